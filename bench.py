@@ -9,12 +9,22 @@ with the trajectory ensemble already resident in HBM.
   python bench.py --gpus N --steps K --warmup W        (N > 1 without a launcher: spawns its N ranks itself)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
   python bench.py --sweep 1,2,4,8                      (one line per N, weak-scaling efficiency on stderr)
+  python bench.py ... --dump-outputs DIR               (also writes the last timed step's results as DIR/*.npy)
+  python bench.py ... --full                           (also every check and side measurement listed below)
 
 Workload (BASELINE.json configs[1], the one the metric is quoted on):
   R = 32768 trajectories per GPU x T = 4096, W = 20, horizon 20, k = 1024, one query;
   synthetic GBM log-returns (shadowing_amd.synthetic), weak scaling R_total = N * 32768.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline
+(`value`, `ms_per_step`); everything else is measured and checked only with --full, and is null in the line
+otherwise.  With --full the line also carries
+  parity       the first result against the reference's golden vector / the CPU oracle, and what the timed
+               steps left behind against the oracle;
+  repeats      the timed region run --repeats times (median / min / max);
+  single_stream_fused, blocking_shadow_api, stages_ms_separate_launches
+               the same steps on one stream (with and without an admission hint), the blocking API call by
+               call, and per-stage times of the separate launches;
   roofline     the dominant kernel (sliding-window scan) against the 8 TB/s HBM peak:
                algorithmic bytes per launch / its average duration, measured live with
                HIP events recorded around that kernel on its own stream, inside the
@@ -82,11 +92,17 @@ def parse():
                          "for the HIP scan -- tests/test_bench_flow_cpu.py runs it with two ranks so that a Python-level bug "
                          "cannot burn a multi-GPU lease")
     ap.add_argument("--repeats", type=int, default=5,
-                    help="the timed region (warm-up + K steps) is run this many times: `value` / `ms_per_step` are the FIRST region's (the "
+                    help="--full: the timed region (warm-up + K steps) is run this many times: `value` / `ms_per_step` are the FIRST region's (the "
                          "contract's K steps), `ms_per_step_repeats` carries median / min / max over all of them")
     ap.add_argument("--no-blocking-api", action="store_true",
                     help="skip the `blocking_shadow_api` block (N = 1, one query): the reference's own call -- one blocking "
                          "PathShadowing.shadow(x, k, cuda=True), README.md:47-57 -- timed call by call outside the headline's region")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the parity checks, the repeated regions, the one-stream and hinted comparisons, "
+                         "the roofline, the stage times, the CPU baseline and the blocking API (off: a plain run times the K steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (distances d, indices idx; float32 / "
+                         "float64) as DIR/<name>.npy -- the inputs are seeded, so two builds can be compared output for output")
     ap.add_argument("--sweep", type=str, default=None,
                     help="comma-separated GPU counts: run each in turn, print one JSON line per N (stdout) and the "
                          "weak-scaling efficiency against the first (stderr)")
@@ -374,6 +390,28 @@ def loop_k(o, queries, n, k):
     return np.asarray(ts)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dst: Path, d: np.ndarray, idx: np.ndarray) -> dict:
+    """The last timed step's results as the caller receives them -- distances (B, k) and (r, t) indices (B, k, 2) --
+    written as dst/distances.npy (float32) and dst/indices.npy (float64, exact for any index).  Above 64 MB in all, a
+    fixed seeded sample of the query rows is written instead, and its row numbers as dst/query_rows.npy."""
+    dst.mkdir(parents=True, exist_ok=True)
+    B = d.shape[0]
+    per_row = d[0].size * 4 + idx[0].size * 8
+    rows = None
+    if B * per_row > DUMP_LIMIT_BYTES:
+        n = max(1, (DUMP_LIMIT_BYTES - 8 * B) // per_row)
+        rows = np.sort(np.random.default_rng(0).choice(B, size=n, replace=False))
+        d, idx = d[rows], idx[rows]
+        np.save(dst / "query_rows.npy", rows.astype(np.float64))
+    np.save(dst / "distances.npy", np.ascontiguousarray(d, dtype=np.float32))
+    np.save(dst / "indices.npy", np.ascontiguousarray(idx, dtype=np.float64))
+    return {"dir": str(dst), "files": ["distances.npy", "indices.npy"] + (["query_rows.npy"] if rows is not None else []),
+            "query_rows": B if rows is None else int(rows.size)}
+
+
 def main():
     args = parse()
     if args.sweep:
@@ -389,6 +427,8 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if args.gpus != world:
         raise SystemExit(f"--gpus {args.gpus} but the launcher started WORLD_SIZE={world} ranks")
+    full = args.full
+    check = full and not args.no_parity          # the comparisons with the golden vectors / the oracle: --full only
     on_gpu = not args.cpu_oracle
     if on_gpu:
         assert torch.cuda.is_available(), "bench.py needs a HIP device"
@@ -470,10 +510,10 @@ def main():
 
     # HIP events around the dominant kernel on every EV_EVERY-th timed step: an event record is a barrier packet of its own
     # on the stream (~5 us for the pair, measured: 112 vs 101 us per step with a pair on every step), so bracketing every
-    # launch would tax the very step time the metric is
+    # launch would tax the very step time the metric is.  They feed the roofline only: a plain run records none
     EV_EVERY = 4
     ev_pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                for _ in range((args.steps + EV_EVERY - 1) // EV_EVERY)] if on_gpu else []
+                for _ in range((args.steps + EV_EVERY - 1) // EV_EVERY)] if (on_gpu and full) else []
     for a, b in ev_pairs:   # materialise the hipEvent handles
         a.record(); b.record()
     sync()
@@ -511,7 +551,7 @@ def main():
                 finished.append((pq, out))
             pending.append((nxt, qi))
             return out
-        ev = ev_pairs[i // EV_EVERY] if (i is not None and i % EV_EVERY == 0) else None
+        ev = ev_pairs[i // EV_EVERY] if (ev_pairs and i is not None and i % EV_EVERY == 0) else None
         si = c % cfg["n_streams"]
         last_query[si] = qi
         # results go to this stream's own buffers (a later step on the same stream overwrites them, in stream order); the
@@ -566,14 +606,14 @@ def main():
         raise SystemExit("the first sharded step gave up (status %d; unexpected)" % sharded.status_max())
     default_sizes = (R, T, W, h, k, B) == (32768, 4096, 20, 20, 1024, 1)
     golden_name = None
-    if not args.no_parity and default_sizes and world == 1 and (REPO / "tests/golden/cfg2_R32768.npz").exists():
+    if check and default_sizes and world == 1 and (REPO / "tests/golden/cfg2_R32768.npz").exists():
         g = np.load(REPO / "tests/golden/cfg2_R32768.npz")
         if syn.sha256(ds_host) == str(g["dataset_sha256"]):
             golden_name = "tests/golden/cfg2_R32768.npz"
             parity = same_result(d0.cpu().numpy(), i0.cpu().numpy(), g["d"], g["idx"], tie_free_order=False)
             if not parity:
                 raise SystemExit("PARITY FAILURE against tests/golden/cfg2_R32768.npz")
-    if not args.no_parity and default_sizes and world in (2, 4, 8) and (REPO / "tests/golden/cfg4_R262144.npz").exists():
+    if check and default_sizes and world in (2, 4, 8) and (REPO / "tests/golden/cfg4_R262144.npz").exists():
         # N > 1: the reference's own output on the concatenated rank blocks (tests/golden/make_golden.py --sharded);
         # every rank vouches for its block's bytes, rank 0 compares the first merged result
         g = np.load(REPO / "tests/golden/cfg4_R262144.npz")
@@ -587,7 +627,7 @@ def main():
             if float(flag.item()) != 1.0:
                 raise SystemExit(f"PARITY FAILURE against {golden_name}")
     parity_first_oracle = None
-    if not args.no_parity and parity is None and B == 1 and (world > 1 or not on_gpu):
+    if check and parity is None and B == 1 and (world > 1 or not on_gpu):
         # other sizes / rank counts: the first merged result against the distributed oracle
         od, oi = expected_by_oracle(0)
         parity_first_oracle = same_result(d0.cpu().numpy(), i0.cpu().numpy(), od, oi, tie_free_order=True)
@@ -596,7 +636,7 @@ def main():
         if float(flag.item()) != 1.0:
             raise SystemExit("PARITY FAILURE of the first merged result against the distributed oracle")
     parity_oracle = None
-    if world == 1 and on_gpu and not args.no_parity and B > 1:
+    if world == 1 and on_gpu and check and B > 1:
         # a batch: the first result of the run against the CPU oracle on a subset of the queries spread over the
         # query chunks of the batched scan (first, around the chunk boundary, last)
         import oracle
@@ -661,9 +701,15 @@ def main():
         elapsed, host_enqueue, bad = timed_region()
     if bad != 0:
         raise SystemExit("candidate buffer overflow during the timed steps (unexpected)")
+    # what the LAST timed step computed, copied to the host before anything else runs on those buffers (written at the end)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        sync()
+        dl, il = finished[-1][1] if sharded is not None else outs[(args.steps - 1) % cfg["n_streams"]]
+        dumped = (dl.cpu().numpy().copy(), il.cpu().numpy().copy())
     # the same region again (the driver's K = 20 steps are 1.7 ms of device time: one region says little about the spread)
     region_ms = [1e3 * elapsed / args.steps]
-    for _ in range(max(0, args.repeats - 1)):
+    for _ in range(max(0, args.repeats - 1) if full else 0):
         el_r, _, bad_r = timed_region()
         if bad_r != 0:
             raise SystemExit("a repeated timed region reported status %d (unexpected)" % bad_r)
@@ -672,7 +718,7 @@ def main():
     # ---- what the timed steps LEFT BEHIND, against the checker: the last result of every stream (unsharded) / the last two
     #      merged results (sharded) must be what their own query batch gives
     rotating = None
-    if not args.no_parity:
+    if check:
         sync()
         left = ([(last_query[si], outs[si]) for si in sorted(last_query)] if sharded is None else list(finished))
         sel = None if B == 1 else sorted({0, min(111, B - 1), min(112, B - 1), B // 2, B - 1})
@@ -700,7 +746,7 @@ def main():
     overlap_mode = bool(flags & _native.FLAG_OVERLAP)
     alg_bytes_const = R * T * 4 + B * W * 4 + B * k * 12    # SURVEY.md 8d (the roofline block below states it again)
     single_stream = None
-    if overlap_mode and sharded is None:
+    if full and overlap_mode and sharded is None:
         # beside the headline: the same K steps on ONE stream as the fused single launch (what an isolated caller gets)
         keep = (step_flags[0], cfg["n_streams"])
         step_flags[0], cfg["n_streams"] = flags & ~_native.FLAG_OVERLAP, 1
@@ -727,7 +773,7 @@ def main():
         el2, _, bad2 = timed_region()
         cfg["hint"] = False
         hinted_ok = None
-        if bad2 == 0 and not args.no_parity:
+        if bad2 == 0 and check:
             sync()
             od, oi = expected_by_oracle(last_query[0])
             hinted_ok = same_result(outs[0][0].cpu().numpy(), outs[0][1].cpu().numpy(), od, oi, tie_free_order=True)
@@ -759,7 +805,7 @@ def main():
     # local scan outside the timed loop (per-GPU kernel time; the timed loop itself carries no events there)
     info = {}
     one_ms = float("nan")
-    if on_gpu:
+    if on_gpu and full:
         one = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         for e in one:
             e.record()
@@ -784,7 +830,7 @@ def main():
                    else "psh::scan_kernel<%s,true,1> (full scan, VALU rejection test)" % wt)
     alg_bytes = R * T * 4 + B * W * 4 + B * k * 12          # one read of the ensemble + query + result
     roofline = None
-    if sharded is None:
+    if full and sharded is None:
         avg_ms = float(np.mean(scan_ms))
         # Launches of different streams are CO-RESIDENT in overlap mode (the blocks of scan i+1 take over a compute unit
         # when scan i's block leaves it): a launch's begin-to-end duration then spans two scans sharing the chip, and the
@@ -863,7 +909,7 @@ def main():
                                 "`achieved_bracketed_launches` = algorithmic bytes / avg_launch_interval_ms (end-to-end interval of consecutive "
                                 "scan launches, HIP events on the launches' own streams); avg_launch_ms is a launch's begin-to-end "
                                 "duration WHILE it shares the chip with the neighbouring scan (profiles/: the kernel trace gives both)")
-    elif on_gpu:
+    elif full and on_gpu:
         achieved = alg_bytes / (one_ms * 1e-3) / 1e9
         roofline = {"bound": "hbm", "kernel": kernel_name, "achieved": round(achieved, 1),
                     "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": None,
@@ -872,7 +918,7 @@ def main():
 
     stages = None
     cpu = None
-    if rank == 0 and world == 1 and on_gpu:
+    if full and rank == 0 and world == 1 and on_gpu:
         # per-stage HIP-event timings of the SEPARATE launches (the fused launch has no stages to bracket); one untimed call
         # first: kernels the timed steps never ran are loaded on their first launch
         _native.scan_topk(ds[:, 0, :], q, k, h=h, workspace=ws, flags=flags | _native.FLAG_NO_FUSE)
@@ -884,7 +930,7 @@ def main():
             cpu["value"] = round(cpu["value"], 1)
 
     blocking = None
-    if rank == 0 and world == 1 and on_gpu and B == 1 and sharded is None and not args.no_blocking_api:
+    if full and rank == 0 and world == 1 and on_gpu and B == 1 and sharded is None and not args.no_blocking_api:
         blocking = blocking_shadow_api(sa, syn, ds, ds_host, q_hosts, W, h, k, None if args.no_parity else expected_by_oracle)
 
     if rank == 0:
@@ -909,7 +955,7 @@ def main():
             "streams": n_streams,
             "ms_per_step_repeats": {"n": len(region_ms), "median": round(float(np.median(region_ms)), 5), "min": round(min(region_ms), 5),
                                     "max": round(max(region_ms), 5), "what": f"the timed region (warm-up {args.warmup} + {args.steps} steps) run "
-                                    f"{len(region_ms)} times; `value` / `ms_per_step` are the first region's"},
+                                    f"{len(region_ms)} times; `value` / `ms_per_step` are the first region's"} if full else None,
             "single_stream_fused": single_stream,
             "blocking_shadow_api": blocking,
             "host_enqueue_ms_per_step": round(1e3 * host_enqueue / args.steps, 5),
@@ -922,7 +968,11 @@ def main():
             "parity_rotating_queries": rotating,
             "cpu_oracle_test_hook": (not on_gpu) or None,
             "fused_launch_gave_up_rerun_as_separate_launches": fused_retry,
+            "full": full,
+            "dumped_outputs": None,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dump_outputs(Path(args.dump_outputs), *dumped)
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if use_pg:
         dist.destroy_process_group()

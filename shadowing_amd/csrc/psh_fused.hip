@@ -47,7 +47,7 @@ __device__ __forceinline__ void g_store32(unsigned* p, unsigned v) {
     __hip_atomic_store((gu32*)(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 // a word the HOST reads (a blocking caller's pinned block): write-through to system scope
-__device__ __forceinline__ void sys_store32(unsigned* p, unsigned v) {
+__device__ __forceinline__ void store32_system(unsigned* p, unsigned v) {
     __hip_atomic_store((gu32*)(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 __device__ __forceinline__ u64 g_load(const u64* p) {
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_fused_kernel(ScanArgs a
     // tuning aid (tools/fused_times.py, -DPSH_TUNING build only sets the pointer): phase boundaries of every wave 0
     auto stamp = [&](int i) { if (a.dbg_times && tid == 0) a.dbg_times[(size_t)blockIdx.x * 8 + i] = (unsigned long long)wall_clock64(); };
     stamp(0);
-    if constexpr (BLK) { if (blockIdx.x == 0 && tid == 0 && f.done) sys_store32(f.done - 1, f.done_val); }   // diagnostics: "started" (psh.h PSH_SHADOW_OFF_STARTED)
+    if constexpr (BLK) { if (blockIdx.x == 0 && tid == 0 && f.done) store32_system(f.done - 1, f.done_val); }   // diagnostics: "started" (psh.h PSH_SHADOW_OFF_STARTED)
     const long long t_start = wall_clock64();
     auto give_up = [&]() -> bool { return wall_clock64() - t_start > f.spin_ticks; };
 
@@ -684,11 +684,11 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_fused_kernel(ScanArgs a
                 const int rk = rankc[j];
                 if (rk >= a.k) continue;
                 const u32x4 o = fl[j];
-                if (lane < 3) sys_store32(lane == 0 ? reinterpret_cast<unsigned*>(f.out_d + rk) : reinterpret_cast<unsigned*>(f.out_idx + 2 * rk + (lane - 1)), o[lane]);
+                if (lane < 3) store32_system(lane == 0 ? reinterpret_cast<unsigned*>(f.out_d + rk) : reinterpret_cast<unsigned*>(f.out_idx + 2 * rk + (lane - 1)), o[lane]);
                 const float* src = f.g_ds + ((int64_t)o[1] - a.r_offset) * f.g_C * f.g_T + (int64_t)o[2];
                 unsigned* dst = reinterpret_cast<unsigned*>(f.g_out + (int64_t)rk * f.g_C * f.g_len);
                 for (int c = 0; c < f.g_C; ++c)
-                    for (int e = lane; e < f.g_len; e += 64) sys_store32(dst + c * f.g_len + e, __float_as_uint(src[(int64_t)c * f.g_T + e]));
+                    for (int e = lane; e < f.g_len; e += 64) store32_system(dst + c * f.g_len + e, __float_as_uint(src[(int64_t)c * f.g_T + e]));
             }
         } else if (tid < mown) {
             const int rk = rankc[tid];
@@ -709,7 +709,7 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_fused_kernel(ScanArgs a
         // publication by the candidate loads and the ranking (several round trips).  OK is only declared over a header
         // that is still armed.
         const bool armed = g_load(&hdr->magic) == PSH_FUSED_MAGIC;
-        sys_store32(reinterpret_cast<unsigned*>(f.status), (good && armed) ? PSH_STATUS_OK_ : PSH_STATUS_RETRY_);   // (a blocking caller's word sits in host memory)
+        store32_system(reinterpret_cast<unsigned*>(f.status), (good && armed) ? PSH_STATUS_OK_ : PSH_STATUS_RETRY_);   // (a blocking caller's word sits in host memory)
         if (f.total) f.total[0] = ntotal;
         if (a.qstate) {                                     // diagnostics / the separate launches' state, kept coherent
             QueryState q;
@@ -736,7 +736,7 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_fused_kernel(ScanArgs a
             if (old + 1u == in_shard) {
                 g_store32(cnt, 0u);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                sys_store32(f.done + shard, f.done_val);
+                store32_system(f.done + shard, f.done_val);
             }
         }
     }

@@ -32,7 +32,7 @@ def _run_bench(nproc: int, extra: list[str], timeout: int = 600):
 
 
 def test_two_rank_gloo_run_of_bench_flow(oracle_mod):
-    res, lines = _run_bench(2, ["--steps", "7", "--warmup", "3", "--rows-per-gpu", "24", "--T", "160", "--k", "50"])
+    res, lines = _run_bench(2, ["--full", "--steps", "7", "--warmup", "3", "--rows-per-gpu", "24", "--T", "160", "--k", "50"])
     assert res.returncode == 0, res.stderr[-3000:]
     assert len(lines) == 1, res.stdout                      # rank 0 prints ONE JSON line, the other rank none
     j = json.loads(lines[0])
@@ -47,7 +47,7 @@ def test_two_rank_gloo_run_of_bench_flow(oracle_mod):
 
 def test_two_rank_gloo_run_with_a_batch_and_a_short_shard(oracle_mod):
     # a batch of queries, and shards with fewer windows than k (2 rows x 9 windows < 40): the padded general path
-    res, lines = _run_bench(2, ["--steps", "3", "--warmup", "1", "--rows-per-gpu", "2", "--T", "48", "--k", "30", "--queries", "3"])
+    res, lines = _run_bench(2, ["--full", "--steps", "3", "--warmup", "1", "--rows-per-gpu", "2", "--T", "48", "--k", "30", "--queries", "3"])
     assert res.returncode == 0, res.stderr[-3000:]
     j = json.loads(lines[0])
     assert j["parity_rotating_queries"]["ok"] is True
@@ -56,7 +56,7 @@ def test_two_rank_gloo_run_with_a_batch_and_a_short_shard(oracle_mod):
 def test_four_rank_gloo_run_with_odd_shards(oracle_mod):
     # four ranks (the driver's N = 4 line), an odd number of rows per rank and a row length that is no multiple of anything,
     # k above a shard's window count: every rank pads, four lists meet in the merge
-    res, lines = _run_bench(4, ["--steps", "5", "--warmup", "2", "--rows-per-gpu", "7", "--T", "131", "--k", "600"])
+    res, lines = _run_bench(4, ["--full", "--steps", "5", "--warmup", "2", "--rows-per-gpu", "7", "--T", "131", "--k", "600"])
     assert res.returncode == 0, res.stderr[-3000:]
     assert len(lines) == 1, res.stdout
     j = json.loads(lines[0])
@@ -67,7 +67,7 @@ def test_four_rank_gloo_run_with_odd_shards(oracle_mod):
 
 def test_two_rank_gloo_run_with_512_query_dates(oracle_mod):
     # configs[2]'s batch size through the sharded flow (B*k*12 bytes per rank in the one all-gather: 6 MiB at k = 1024; here small)
-    res, lines = _run_bench(2, ["--steps", "2", "--warmup", "1", "--rows-per-gpu", "6", "--T", "120", "--k", "24", "--queries", "512"])
+    res, lines = _run_bench(2, ["--full", "--steps", "2", "--warmup", "1", "--rows-per-gpu", "6", "--T", "120", "--k", "24", "--queries", "512"])
     assert res.returncode == 0, res.stderr[-3000:]
     j = json.loads(lines[0])
     assert j["config"]["queries"] == 512 and j["parity_rotating_queries"]["ok"] is True
@@ -75,7 +75,7 @@ def test_two_rank_gloo_run_with_512_query_dates(oracle_mod):
 
 
 def test_one_rank_hook_and_launcher_mismatch(oracle_mod):
-    res, lines = _run_bench(1, ["--steps", "2", "--warmup", "1", "--rows-per-gpu", "8", "--T", "100", "--k", "16"])
+    res, lines = _run_bench(1, ["--full", "--steps", "2", "--warmup", "1", "--rows-per-gpu", "8", "--T", "100", "--k", "16"])
     assert res.returncode == 0, res.stderr[-3000:]
     assert json.loads(lines[0])["parity_vs_golden"] is True
     # --gpus that disagrees with the launcher's world size is refused before anything runs
@@ -83,6 +83,43 @@ def test_one_rank_hook_and_launcher_mismatch(oracle_mod):
            "--master-port", str(_free_port()), str(REPO / "bench.py"), "--gpus", "4", "--cpu-oracle", "--steps", "1"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=str(REPO))
     assert res.returncode != 0 and "WORLD_SIZE=2" in (res.stderr + res.stdout)
+
+
+def test_plain_run_times_only_and_dumps_the_last_step(oracle_mod, tmp_path):
+    """Without --full the line carries the headline and nothing measured or checked beside it; --dump-outputs writes
+    the last timed step's (d, idx) -- step 6 of 7 is query batch 6 % 4 = 2 -- which is what the oracle gives for it."""
+    sys.path.insert(0, str(REPO))
+    import bench
+    from shadowing_amd import synthetic as syn
+    res, lines = _run_bench(2, ["--steps", "7", "--warmup", "3", "--rows-per-gpu", "24", "--T", "160", "--k", "50",
+                                "--dump-outputs", str(tmp_path / "out")])
+    assert res.returncode == 0, res.stderr[-3000:]
+    j = json.loads(lines[0])
+    assert j["full"] is False and j["steps"] == 7 and j["ms_per_step"] > 0 and j["value"] > 0
+    for key in ("parity_vs_golden", "parity_rotating_queries", "roofline", "cpu_baseline", "ms_per_step_repeats",
+                "single_stream_fused", "blocking_shadow_api", "stages_ms_separate_launches"):
+        assert j[key] is None, key
+    d = np.load(tmp_path / "out" / "distances.npy")
+    idx = np.load(tmp_path / "out" / "indices.npy")
+    assert d.dtype == np.float32 and d.shape == (1, 50) and idx.dtype == np.float64 and idx.shape == (1, 50, 2)
+    q = syn.single_query(20, 1002)[None, :]
+    parts = [oracle_mod.scan_topk(syn.dataset(24, 160, seed=r), q, 50, h=20, r_offset=24 * r) for r in range(2)]
+    od, oi = bench.host_merge(np.concatenate([p[0] for p in parts], 1), np.concatenate([p[1] for p in parts], 1), 50)
+    assert np.array_equal(d.view(np.uint32), od.view(np.uint32)) and np.array_equal(idx, oi.astype(np.float64))
+
+
+def test_dump_keeps_a_seeded_sample_of_a_large_output(tmp_path, monkeypatch):
+    m = _bench_module()
+    monkeypatch.setattr(m, "DUMP_LIMIT_BYTES", 10 * (4 * 8 + 8 * 16) + 100)
+    d = np.arange(40 * 8, dtype=np.float32).reshape(40, 8)
+    idx = np.arange(40 * 16, dtype=np.int32).reshape(40, 8, 2)
+    info = m.dump_outputs(tmp_path / "a", d, idx)
+    rows = np.load(tmp_path / "a" / "query_rows.npy").astype(np.int64)
+    assert info["query_rows"] == rows.size <= 10 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "distances.npy"), d[rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "indices.npy"), idx[rows].astype(np.float64))
+    m.dump_outputs(tmp_path / "b", d, idx)
+    assert np.array_equal(np.load(tmp_path / "b" / "query_rows.npy"), rows.astype(np.float64))
 
 
 def _line(n, value, ms, world=None, parity=True, rot=True):

@@ -12,8 +12,8 @@ cd /tmp
 python -m shadowing_amd._build --tuning > /dev/null 2>&1
 export PSH_LIB=$R/shadowing_amd/lib/libpsh_hip_tuning.so
 for d in 0 8; do
-  PSH_DBG=$d timeout 300 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_BUSY_CYCLES --output-format csv -d $OUT/pmc_d$d/pmc_1 -o p -- python $R/bench.py --steps 6 --warmup 2 --queries 512 --no-cpu-baseline --no-parity > $OUT/pmc_$d.log 2>&1
-  PSH_DBG=$d timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_d$d -o t -- python $R/bench.py --steps 6 --warmup 2 --queries 512 --no-cpu-baseline --no-parity > $OUT/trace_$d.log 2>&1
+  PSH_DBG=$d timeout 300 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_BUSY_CYCLES --output-format csv -d $OUT/pmc_d$d/pmc_1 -o p -- python $R/bench.py --full --steps 6 --warmup 2 --queries 512 --no-cpu-baseline --no-parity > $OUT/pmc_$d.log 2>&1
+  PSH_DBG=$d timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_d$d -o t -- python $R/bench.py --full --steps 6 --warmup 2 --queries 512 --no-cpu-baseline --no-parity > $OUT/trace_$d.log 2>&1
 done
 python - <<PY
 import csv, glob, collections

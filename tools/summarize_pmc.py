@@ -29,7 +29,7 @@ if "--traffic" in sys.argv:
     cands = [kn for (kn, cn) in means if cn == "FETCH_SIZE" and ("stream_scan_kernel" in kn or "scan_fused_kernel" in kn or "scan_mx_kernel" in kn
                                                                   or "scan_kernel<20, true, 1>" in kn or "scan_kernel<20,true,1>" in kn)]
     if cands:
-        # (bench.py's default run holds the overlap steps AND, for comparison, the same steps as fused launches: the
+        # (bench.py --full holds the overlap steps AND, for comparison, the same steps as fused launches: the
         #  headline's dominant kernel is the overlap scan)
         pref = [k for k in cands if "stream_scan_kernel" in k]
         kn = pref[0] if pref else max(cands, key=lambda k: means[(k, "FETCH_SIZE")])
@@ -47,7 +47,7 @@ if "--traffic" in sys.argv:
                            "2 x FETCH_SIZE x 1024 (MI355X_MICROARCH.md, HBM section); WRITE_SIZE taken as is",
              "hbm_bytes_per_launch": int(2 * fetch * 1024 + write * 1024),
              "algorithmic_bytes_per_launch": R * T * 4 + B * W * 4 + B * k * 12,
-             "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, no trace options) -- python bench.py "
+             "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, no trace options) -- python bench.py --full "
                        "--steps 5 --warmup 2; mean over the launches"}
         with open(dst, "w") as f:
             json.dump(j, f, indent=1)
@@ -73,7 +73,7 @@ if "--mq" in sys.argv:
              "units": "SQ_VALU_MFMA_BUSY_CYCLES: cycles summed over the SIMDs; SQ_ACTIVE_INST_VALU: quad-cycles summed over the SIMDs "
                       "(it includes the issue of the MFMAs themselves); launch cycles = GRBM_GUI_ACTIVE / 8 XCDs; FETCH_SIZE x 2 "
                       "(gfx950 correction) + WRITE_SIZE",
-             "source": "rocprofv3 --pmc passes (separate runs, no trace options) -- python bench.py --steps 2 --warmup 1 --queries 512"}
+             "source": "rocprofv3 --pmc passes (separate runs, no trace options) -- python bench.py --full --steps 2 --warmup 1 --queries 512"}
         with open(dst, "w") as f:
             json.dump(j, f, indent=1)
         print("wrote", dst, j)
