@@ -505,6 +505,31 @@ int psh_weighted_moments(int device, void* stream, const float* values, const do
 int psh_realized_variance(int device, void* stream, const float* x, int64_t n_rows, int64_t row_stride, int len,
                           const int* Ts, int nT, int vol, float* out);
 
+/*
+ * Hedged Monte Carlo (Potters, Bouchaud, Sestovic 2001) on the k shadowing paths of each of B dates: the option prices,
+ * Black-Scholes implied vols and strikes of a smile.  The method, in full, heads shadowing_amd/csrc/psh_hmc.hip (and
+ * README "Option pricing"); shadowing_amd/pricing.py is its numpy twin.
+ *   dlnx:  device float32 log-returns, row b * k + i (path i of date b) starts at dlnx + (b * k + i) * row_stride and holds
+ *          `len` samples (the out-context view of psh_gather_paths output: dlnx = paths + c * (W + h) + W,
+ *          row_stride = C * (W + h), len = h -- no copy);
+ *   weights: device B x k float64 (normalised here by their sum), or NULL: uniform;
+ *   Ts: HOST array of nT <= 64 maturities in samples, 1 <= T <= len;  Ms: HOST array of nM <= 64 rescaled log-moneyness;
+ *   degree: 1..5 (basis u^0..u^degree);  kind: PSH_HMC_OTM / PSH_HMC_CALL / PSH_HMC_PUT;
+ *   out_price, out_iv, out_strike: device B x nT x nM float64;  out_sigma: device B x nT (sigma_T) or NULL;
+ *   out_status: device B int32 (PSH_HMC_STATUS_* bits; a date with a bit set has NaN results) or NULL.
+ * k > PSH_MAX_K or degree > 5: PSH_ERR_UNSUPPORTED.  Sums in double, fixed order: two calls give identical bits.
+ */
+#define PSH_HMC_OTM   0        /* a call for M >= 0, a put for M < 0 */
+#define PSH_HMC_CALL  1
+#define PSH_HMC_PUT   2
+#define PSH_HMC_STATUS_OK         0
+#define PSH_HMC_STATUS_NONFINITE  1   /* a path with non-zero weight has a non-finite return in [0, max Ts) */
+#define PSH_HMC_STATUS_WEIGHTS    2   /* a non-finite weight, or a weight sum that is not > 0 */
+int psh_hedged_mc(int device, void* stream, const float* dlnx, int64_t row_stride, int B, int k, int len,
+                  const double* weights, double x_init, double rate, const int* Ts, int nT, const double* Ms, int nM,
+                  int degree, int kind, double* out_price, double* out_iv, double* out_strike, double* out_sigma,
+                  int32_t* out_status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,12 +11,13 @@ from .path_embedding import (ArrayType, ContextManagerBase, CrossChannelContext,
                              ImputationContext, PathEmbedding, PredictionContext)
 from .path_shadowing import PathShadowing, PendingShadow, select_cartesian_product
 from .plotting import plot_closest, plot_shadow, plot_volatility
+from .pricing import PriceData, Smile, compute_smile
 from .statistics import realized_variance
 
 __all__ = [
     "ArrayType", "ContextManagerBase", "PredictionContext", "ImputationContext", "CrossChannelContext",
     "PathEmbedding", "Identity", "Foveal", "PathDistance", "RelativeMSE", "PathShadowing",
     "select_cartesian_product", "DiscreteProba", "Softmax", "Uniform", "realized_variance",
-    "plot_closest", "plot_shadow", "plot_volatility",
+    "plot_closest", "plot_shadow", "plot_volatility", "PriceData", "Smile", "compute_smile",
 ]
 __version__ = "0.1.0"

@@ -17,6 +17,10 @@ PSH_OK = 0
 PSH_VERSION = 3          # include/psh.h: 2: psh_profile.tau_hint, psh_candidates_layout; 3: psh_shadow_blocking
 PSH_STATUS_OK, PSH_STATUS_OVERFLOW, PSH_STATUS_RETRY = 0, 1, 2
 PSH_MAX_W, PSH_MAX_K, PSH_MAX_B_PER_LAUNCH = 256, 16384, 1024
+# psh_hedged_mc (include/psh.h)
+PSH_HMC_OTM, PSH_HMC_CALL, PSH_HMC_PUT = 0, 1, 2
+PSH_HMC_STATUS_OK, PSH_HMC_STATUS_NONFINITE, PSH_HMC_STATUS_WEIGHTS = 0, 1, 2
+PSH_HMC_MAX_T = PSH_HMC_MAX_M = 64
 # psh_profile.flags (include/psh.h)
 FLAG_UNSORTED, FLAG_FILTER_VALU, FLAG_EMBED_DENSE, FLAG_ROWS_GENERIC, FLAG_NO_FUSE, FLAG_RESERVE_CUS, FLAG_EMBED_MX, FLAG_EMBED_TAPS, FLAG_EMBED_PLAN_KEEP, FLAG_EMBED_MX_SPLIT, FLAG_SELECT_ONE_BLOCK, FLAG_OVERLAP, FLAG_MQ_F16, FLAG_LONG_LOOP = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192
 
@@ -44,7 +48,7 @@ EXPORTS = ("psh_version", "psh_strerror", "psh_last_hip_error", "psh_workspace_b
            "psh_embedded_supported", "psh_embed_plan_offset", "psh_candidates_layout", "psh_workspace_init", "psh_last_comm_error", "psh_comm_unique_id", "psh_comm_create",
            "psh_comm_destroy", "psh_comm_world", "psh_exchange_merge", "psh_stream_create_reserving", "psh_stream_destroy",
            "psh_weighted_moments", "psh_realized_variance", "psh_count_nonfinite", "psh_smear_nonfinite", "psh_rows_nonfinite",
-           "psh_shadow_block_layout", "psh_shadow_blocking")
+           "psh_shadow_block_layout", "psh_shadow_blocking", "psh_hedged_mc")
 
 _lib = None
 
@@ -144,6 +148,9 @@ def load() -> C.CDLL:
     L.psh_weighted_moments.argtypes = [i32, vp, vp, vp, i32, i32, i32, vp, vp]
     L.psh_realized_variance.restype = i32
     L.psh_realized_variance.argtypes = [i32, vp, vp, i64, i64, i32, C.POINTER(C.c_int), i32, i32, vp]
+    L.psh_hedged_mc.restype = i32
+    L.psh_hedged_mc.argtypes = [i32, vp, vp, i64, i32, i32, i32, vp, C.c_double, C.c_double, C.POINTER(C.c_int), i32,
+                                C.POINTER(C.c_double), i32, i32, i32, vp, vp, vp, vp, vp]
     L.psh_gather_paths.restype = i32
     L.psh_gather_paths.argtypes = [i32, vp, vp, i64, i64, i64, i64, vp, i64, i32, vp]
     if L.psh_version() != PSH_VERSION:
@@ -939,6 +946,46 @@ def realized_variance(x: torch.Tensor, Ts, vol: bool = False) -> torch.Tensor | 
     arr = (C.c_int * len(Ts))(*Ts)
     _check(load().psh_realized_variance(x.device.index, _stream_ptr(x.device), x.data_ptr(), n_rows, row_stride, L, arr, len(Ts),
                                         1 if vol else 0, out.data_ptr()), "psh_realized_variance")
+    return out
+
+
+def hedged_mc(dlnx: torch.Tensor, weights: torch.Tensor | None, Ts, Ms, x_init: float = 100.0, rate: float = 0.0,
+              degree: int = 3, kind: int = PSH_HMC_OTM) -> dict:
+    """psh_hedged_mc on a float32 HIP tensor of log-returns (B, k, L) whose rows lie a constant stride apart (contiguous,
+    or the out-context view `paths[:, :, c, W:]` of gathered paths -- no copy); weights (B, k) float64 or None (uniform).
+    Returns device tensors: price / iv / strike (B, nT, nM) float64, sigma (B, nT) float64, status (B,) int32."""
+    x = dlnx
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise NativeLibraryError(f"dlnx must be a tensor on a HIP device (got {type(x).__name__}); there is no CPU path here")
+    if x.dtype != torch.float32:
+        raise TypeError(f"dlnx must be torch.float32, got {x.dtype}")
+    if x.dim() != 3:
+        raise ValueError("dlnx must be (B, k, L)")
+    B, k, L = x.shape
+    rows = _uniform_rows(x)
+    if rows is None or rows[1] < L:
+        x = x.contiguous()
+        rows = _uniform_rows(x)
+    row_stride = rows[1]
+    w_ptr = None
+    if weights is not None:
+        w = _dev_tensor(weights, torch.float64, "weights")
+        if tuple(w.shape) != (B, k):
+            raise ValueError(f"weights must be (B, k) = ({B}, {k}), got {tuple(w.shape)}")
+        if w.device != x.device:
+            raise ValueError("weights and dlnx must be on the same device")
+        w_ptr = w.data_ptr()
+    Ts = [int(T) for T in Ts]
+    Ms = [float(M) for M in Ms]
+    nT, nM = len(Ts), len(Ms)
+    out = {name: torch.empty((B, nT, nM), dtype=torch.float64, device=x.device) for name in ("price", "iv", "strike")}
+    out["sigma"] = torch.empty((B, nT), dtype=torch.float64, device=x.device)
+    out["status"] = torch.empty((B,), dtype=torch.int32, device=x.device)
+    _check(load().psh_hedged_mc(x.device.index, _stream_ptr(x.device), x.data_ptr(), row_stride, B, k, L, w_ptr,
+                                float(x_init), float(rate), (C.c_int * max(nT, 1))(*Ts), nT,
+                                (C.c_double * max(nM, 1))(*Ms), nM, int(degree), int(kind), out["price"].data_ptr(),
+                                out["iv"].data_ptr(), out["strike"].data_ptr(), out["sigma"].data_ptr(),
+                                out["status"].data_ptr()), "psh_hedged_mc")
     return out
 
 

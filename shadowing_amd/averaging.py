@@ -48,14 +48,16 @@ except Exception:  # noqa: BLE001
             super().__init__(None)
 
     class Softmax(DiscreteProba):
-        """Gaussian weights exp(-d^2 / (2 eta^2)), normalised over axis 1 (the k paths)."""
+        """Gaussian weights exp(-d^2 / (2 eta^2)), normalised over axis 1 (the k paths) -- over the only axis for the
+        (k,) distances of one date (the README's `Softmax(distances[-1, :], eta)`)."""
 
         def __init__(self, distances: np.ndarray, eta: float | None):
             d = np.asarray(distances, dtype=np.float64)
+            axis = 0 if d.ndim == 1 else 1
             if eta is None:
                 w = np.ones_like(d)
             else:
                 z = -(d ** 2) / (2.0 * float(eta) ** 2)
-                z = z - z.max(axis=1, keepdims=True)
+                z = z - z.max(axis=axis, keepdims=True)
                 w = np.exp(z)
-            super().__init__(w / w.sum(axis=1, keepdims=True))
+            super().__init__(w / w.sum(axis=axis, keepdims=True))

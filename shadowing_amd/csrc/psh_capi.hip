@@ -1444,4 +1444,33 @@ int psh_realized_variance(int device, void* stream, const float* x, int64_t n_ro
     return PSH_OK;
 }
 
+int psh_hedged_mc(int device, void* stream, const float* dlnx, int64_t row_stride, int B, int k, int len,
+                  const double* weights, double x_init, double rate, const int* Ts, int nT, const double* Ms, int nM,
+                  int degree, int kind, double* out_price, double* out_iv, double* out_strike, double* out_sigma,
+                  int32_t* out_status) {
+    if (!dlnx || !Ts || !Ms || !out_price || !out_iv || !out_strike || B <= 0 || k <= 0 || len <= 0 || row_stride < len ||
+        nT <= 0 || nM <= 0 || degree < 1 || kind < PSH_HMC_OTM || kind > PSH_HMC_PUT || !std::isfinite(x_init) ||
+        !(x_init > 0.0) || !std::isfinite(rate))
+        return PSH_ERR_ARG;
+    if (k > PSH_MAX_K || degree > 5 || nT > PSH_HMC_MAX_T || nM > PSH_HMC_MAX_M) return PSH_ERR_UNSUPPORTED;
+    if ((int64_t)B * k * row_stride >= ((int64_t)1 << 40) || (int64_t)B * nT * ((nM + PSH_HMC_SG - 1) / PSH_HMC_SG) >= ((int64_t)1 << 31))
+        return PSH_ERR_UNSUPPORTED;
+    HmcArgs a{};
+    a.x = dlnx; a.row_stride = row_stride; a.B = B; a.k = k; a.len = len; a.w = weights; a.x_init = x_init; a.rate = rate;
+    a.nT = nT; a.nM = nM; a.degree = degree; a.kind = kind; a.ngroups = (nM + PSH_HMC_SG - 1) / PSH_HMC_SG;
+    for (int i = 0; i < nT; ++i) {
+        if (Ts[i] < 1 || Ts[i] > len) return PSH_ERR_ARG;
+        a.Ts[i] = Ts[i];
+    }
+    for (int i = 0; i < nM; ++i) {
+        if (!std::isfinite(Ms[i])) return PSH_ERR_ARG;
+        a.Ms[i] = Ms[i];
+    }
+    a.price = out_price; a.iv = out_iv; a.strike = out_strike; a.sigma = out_sigma; a.status = out_status;
+    DeviceGuard g(device);
+    if (!g.ok) { snprintf(g_hip_err, sizeof(g_hip_err), "hipSetDevice(%d) failed", device); return PSH_ERR_HIP; }
+    HIP_TRY(launch_hedged_mc(a, (hipStream_t)stream));
+    return PSH_OK;
+}
+
 }  // extern "C"

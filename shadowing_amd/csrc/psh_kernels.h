@@ -380,4 +380,25 @@ hipError_t launch_smear_nonfinite(const float* ds, int64_t R, int64_t C, int64_t
 hipError_t launch_moments(const MomentsArgs& a, hipStream_t s);
 hipError_t launch_realized_variance(const RvArgs& a, hipStream_t s);
 
+// psh_hmc.hip: hedged Monte Carlo on the shadowing paths of a date (psh_hedged_mc)
+#define PSH_HMC_SG 3              // strikes a block solves (the Gram matrix of a step is shared by them)
+#define PSH_HMC_MAX_T 64
+#define PSH_HMC_MAX_M 64
+struct HmcArgs {
+    const float* x;           // row b * k + i starts at x + (b * k + i) * row_stride
+    int64_t row_stride;
+    int B, k, len;
+    const double* w;          // (B, k), or nullptr: uniform
+    double x_init, rate;
+    int nT, nM, degree, kind, ngroups;   // ngroups = ceil(nM / PSH_HMC_SG)
+    int Ts[PSH_HMC_MAX_T];
+    double Ms[PSH_HMC_MAX_M];
+    double* price;            // (B, nT, nM)
+    double* iv;
+    double* strike;
+    double* sigma;            // (B, nT) or nullptr
+    int32_t* status;          // (B) or nullptr
+};
+hipError_t launch_hedged_mc(const HmcArgs& a, hipStream_t s);
+
 }  // namespace psh

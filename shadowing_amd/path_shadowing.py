@@ -897,6 +897,68 @@ class PathShadowing:
             self._predict_scope = None
         return np.concatenate(means), np.concatenate(stds)
 
+    # ------------------------------------------------------------------ option pricing (README "Option pricing")
+    def _smile_weights(self, proba_name: str, distances: np.ndarray, eta: float | None):
+        """(B, k) float64 weights of the installed averaging class for these distances, or None for uniform ones."""
+        proba = self.init_averaging_proba(proba_name, distances, eta)
+        w = getattr(proba, "weights", None)
+        if w is None:
+            return None
+        w = np.asarray(w, dtype=np.float64)
+        while w.ndim > 2 and w.shape[-1] == 1:
+            w = w[..., 0]
+        return np.ascontiguousarray(np.broadcast_to(w, distances.shape), dtype=np.float64)
+
+    def smile_from_paths(self, distances: np.ndarray, paths, Ts, Ms, proba_name: str = "softmax", eta: float | None = None,
+                         r: float = 0.0, x_init: float = 100.0, channel: int = 0, degree: int = 3, kind: str = "otm"):
+        """Hedged Monte Carlo smile (pricing.compute_smile) of the out-context of the k shadowing paths of every query,
+        weighted by the averaging class, as predict_from_paths() weighs its statistic.  `paths` (B, k, C, T_x + h) are
+        log-returns; prices start at x_init.  Numpy paths take the host path, HIP tensors the psh_hedged_mc kernel."""
+        if not isinstance(self.context, PredictionContext):
+            raise NotImplementedError("smile_from_paths: only a PredictionContext has an out-context to price on")
+        from .pricing import smile_from_log_returns
+        future = self.context.select_out_context(paths)[:, :, channel, :]
+        d = distances.detach().cpu().numpy() if isinstance(distances, torch.Tensor) else np.asarray(distances)
+        w = self._smile_weights(proba_name, d, eta)
+        cuda = isinstance(future, torch.Tensor) and future.is_cuda
+        return smile_from_log_returns(future, w, Ts, Ms, x_init, r, degree=degree, kind=kind, cuda=cuda)
+
+    def smile(self, x_context: ArrayType, k: int, Ts, Ms, eta: float | None = None, proba_name: str = "softmax",
+              r: float = 0.0, x_init: float = 100.0, channel: int = 0, degree: int = 3, kind: str = "otm",
+              n_dataset_splits: int = 1, n_context_splits: int = 1, cuda: bool = False):
+        """shadow() + smile_from_paths() over `n_context_splits` batches of queries.  With cuda=True on a natively scanned
+        configuration the gathered paths stay in HBM: the (B, k) distances come to the host for the averaging class's
+        weights, the weights go back up, psh_hedged_mc prices on the out-context view of the paths, and only the
+        (B, nT, nM) results come down.  Anything else (k > PSH_MAX_K included) prices the host results of shadow()."""
+        from .pricing import Smile, smile_from_log_returns
+        if not isinstance(self.context, PredictionContext):
+            raise NotImplementedError("smile: only a PredictionContext has an out-context to price on")
+        x = _torch(_dim_array(x_context))
+        n = x.shape[0]
+        y = None
+        parts = []
+        for rows in torch.arange(n).split(max(1, n // n_context_splits)):
+            xr = x[rows, ...]
+            if cuda and k <= _native.PSH_MAX_K:
+                y = self._dataset_tensor() if y is None else y
+                if self._native_ok(xr, y, k):
+                    d, idx, ds = self._native_scan(xr, y, k)
+                    self.last_path = self._served_by
+                    W = xr.shape[-1]
+                    paths = _native.gather_paths(ds, idx, W + self.context.get_out_times())
+                    (d_host,) = self._to_host(d)
+                    w = self._smile_weights(proba_name, d_host, eta)
+                    wt = None if w is None else torch.from_numpy(w.copy()).to(paths.device)
+                    future = self.context.select_out_context(paths)[:, :, channel, :]
+                    parts.append(smile_from_log_returns(future, wt, Ts, Ms, x_init, r, degree=degree, kind=kind, cuda=True))
+                    continue
+            d, paths, _ = self.shadow(xr, k, n_dataset_splits, cuda)
+            parts.append(self.smile_from_paths(d, paths, Ts, Ms, proba_name, eta, r, x_init, channel, degree, kind))
+        cat = lambda name: np.concatenate([getattr(p, name) for p in parts])   # noqa: E731
+        p0 = parts[0]
+        return Smile(cat("prices"), cat("ivs"), cat("strikes"), cat("sigma"), p0.Ts, p0.Ms, kind, cat("status"),
+                     p0.x_init, p0.r)
+
 
 _MOMENT_CLASSES: dict = {}      # averaging class -> its avg / std ARE the weighted moments of its `weights` (probed once)
 
