@@ -516,7 +516,7 @@ int psh_realized_variance(int device, void* stream, const float* x, int64_t n_ro
  *   Ts: HOST array of nT <= 64 maturities in samples, 1 <= T <= len;  Ms: HOST array of nM <= 64 rescaled log-moneyness;
  *   degree: 1..5 (basis u^0..u^degree);  kind: PSH_HMC_OTM / PSH_HMC_CALL / PSH_HMC_PUT;
  *   out_price, out_iv, out_strike: device B x nT x nM float64;  out_sigma: device B x nT (sigma_T) or NULL;
- *   out_status: device B int32 (PSH_HMC_STATUS_* bits; a date with a bit set has NaN results) or NULL.
+ *   out_status: device B int32 (PSH_HMC_STATUS_* bits; NONFINITE / WEIGHTS: all the date's results are NaN) or NULL.
  * k > PSH_MAX_K or degree > 5: PSH_ERR_UNSUPPORTED.  Sums in double, fixed order: two calls give identical bits.
  */
 #define PSH_HMC_OTM   0        /* a call for M >= 0, a put for M < 0 */
@@ -525,6 +525,8 @@ int psh_realized_variance(int device, void* stream, const float* x, int64_t n_ro
 #define PSH_HMC_STATUS_OK         0
 #define PSH_HMC_STATUS_NONFINITE  1   /* a path with non-zero weight has a non-finite return in [0, max Ts) */
 #define PSH_HMC_STATUS_WEIGHTS    2   /* a non-finite weight, or a weight sum that is not > 0 */
+#define PSH_HMC_STATUS_ILL_CONDITIONED 4   /* a maturity whose fit is nearly singular or whose hedge is nearly riskless
+                                              (psh_hmc.hip): its prices and IVs are NaN, its strikes and sigma stay */
 int psh_hedged_mc(int device, void* stream, const float* dlnx, int64_t row_stride, int B, int k, int len,
                   const double* weights, double x_init, double rate, const int* Ts, int nT, const double* Ms, int nM,
                   int degree, int kind, double* out_price, double* out_iv, double* out_strike, double* out_sigma,

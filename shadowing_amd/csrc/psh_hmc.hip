@@ -19,6 +19,26 @@
 //       beta_0..beta_P: an unknown whose pivot is <= 1e-10 times its diagonal entry of G (or whose diagonal is 0) is
 //       dropped -- set to 0, its row and column removed;
 //       V_n = sum_a gamma_a psi_a (the hedge phi_n = sum_a beta_a psi_a).
+//   * Ill-conditioned: the maturity's prices and IVs are NaN (its strikes and sigma stay) and the date's status word gets
+//     PSH_HMC_STATUS_ILL_CONDITIONED when, at some step n < T, a kept unknown has a pivot below its diagonal times
+//       - TAU_SING = 1e-6, for any unknown: the fit is nearly singular (on heavy tails, a few outlying paths decide the
+//         top powers of u); or
+//       - TAU_ILL = 0.2, for beta_0 at a step n > 0: beta_0's pivot over sum_i w_i D_i^2 is the share of D's weighted
+//         second moment that no polynomial of degree P in S_n explains.  A small one means the hedge is almost riskless,
+//         V and phi D can barely be told apart, and the split between gamma and beta amplifies rounding step after step.
+//         (At n = 0 the fit is the 2 x 2 regression on {1, D}: a drifting first step alone cannot amplify anything.)
+//     Evidence (numpy twin against tests/_hmc_reference.py, both float64; "agree" is 1e-9 relative + 1e-9 absolute):
+//     - Drift sweep: k = 200, L = 20, Ts 5 / 20, returns c + e N(0, 1), c in {0, +-0.001, 0.003, +-0.01}, e 1e-2 .. 1e-6,
+//       degrees 1 / 3 / 5.  Every case with a beta_0 ratio >= 0.35 agrees to 2.6e-13 x_init; every case that does not
+//       agree has a ratio <= 0.07 (degree 5: 0.058 .. 0.07; degree 3: <= 8e-3; degree 1: <= 8e-5), and below ~1e-2 prices
+//       reach 1e10 .. 1e62 on a spot of 100.  There the minimum pivot ratio over all unknowns is no guide: drifting
+//       degree-3 data at 9.2e-4 do not agree, GBM with a spread of vols at degree 5, k = 2000, T = 75, reaches 2.2e-4
+//       and agrees (Hermite He_a(u) in place of u^a: 2.6e-3 and 3.3e-4, no better).
+//     - Student-t 2.5 (tests/_adversarial.py), 24 dates of k = 1000, T = 75, degrees 3 / 4 / 5: every date that does
+//       not agree (8e-8 .. 1e-2 absolute, prices from -4 to 584 where the rest give ~6.4) has a minimum kept pivot ratio
+//       <= 7.5e-8 (1.2e-7 on other Student-t draws), while its beta_0 ratio stays >= 0.8; every date at >= 4e-7 agrees.
+//       GBM data stay at >= 2e-4 at degree 5.
+//     - Not covered: an unknown whose pivot rounds to either side of the 1e-10 drop rule in two implementations.
 //   * price = V_0; implied vol: Black-Scholes (spot x_init, strike K, tau_T, rate) inverted by exactly 100 bisection
 //     halvings on [1e-4, 5]; NaN when the price lies outside [BS(1e-4), BS(5)].
 //   * Non-finite weights, a weight sum that is not > 0, or a non-finite return in [0, max Ts) of a path with non-zero
@@ -30,7 +50,8 @@
 // sum w u^m, sum w u^m D, sum w u^m D^2 (m <= 2P: every entry of G) and of h for the block's strikes; per-thread partials in
 // double, wave sums by butterfly, the waves added in a fixed order (bitwise repeatable).  Wave 0 factorises G (lane i holds
 // row i), lane s of the block then solves for strike s and leaves gamma in LDS for the next step's Horner.  The tail of the
-// block inverts Black-Scholes by the same bisection as pricing.py.  No workspace.
+// block inverts Black-Scholes by the same bisection as pricing.py.  No workspace.  The status words are zeroed on the
+// stream before the launch and OR-ed by the g == 0 block of each (date, maturity), whichever finishes first.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -42,6 +63,8 @@ namespace psh {
 
 #define PSH_HMC_THREADS 256
 #define PSH_HMC_WAVES (PSH_HMC_THREADS / 64)
+#define PSH_HMC_TAU_ILL 0.2
+#define PSH_HMC_TAU_SING 1e-6
 
 namespace {
 
@@ -166,10 +189,9 @@ __global__ __launch_bounds__(PSH_HMC_THREADS) void hmc_kernel(HmcArgs a) {
             a.strike[obase + tid] = NAN;
         }
         if (tid == 0 && g == 0 && a.sigma) a.sigma[(int64_t)b * a.nT + it] = NAN;
-        if (tid == 0 && g == 0 && it == 0 && a.status) a.status[b] = bad;
+        if (tid == 0 && g == 0 && it == 0 && a.status) atomicOr(&a.status[b], bad);
         return;                                              // (block-uniform)
     }
-    if (tid == 0 && g == 0 && it == 0 && a.status) a.status[b] = PSH_HMC_STATUS_OK;
     const double invw = 1.0 / wsum;
     const double tau = (double)T / 252.0;
     const double sigma = sqrt((252.0 / (double)T) * (tot[1] * invw));
@@ -186,6 +208,7 @@ __global__ __launch_bounds__(PSH_HMC_THREADS) void hmc_kernel(HmcArgs a) {
     if (tid == 0 && g == 0 && a.sigma) a.sigma[(int64_t)b * a.nT + it] = sigma;
 
     double mu1 = 0.0, isd1 = 0.0;                            // the standardisation of step n+1 (coef's basis)
+    bool ill = false;                                        // (wave 0, lane-uniform) the rule of the header
     for (int n = T - 1; n >= 0; --n) {
         // ---- mean / spread of S_n over the weighted paths (u = 0 when they all share one price: always at n = 0)
         double mu0 = x0, isd0 = 0.0;
@@ -298,6 +321,7 @@ __global__ __launch_bounds__(PSH_HMC_THREADS) void hmc_kernel(HmcArgs a) {
             for (int j = 0; j < NF; ++j) {
                 const double dj = __shfl(A[j], j, 64), gj = __shfl(diag0, j, 64);
                 const bool keep = gj > 0.0 && dj > 1e-10 * gj;
+                ill = ill || (keep && (dj < PSH_HMC_TAU_SING * gj || (j == NB && n > 0 && dj < PSH_HMC_TAU_ILL * gj)));
                 const double ljj = keep ? sqrt(dj) : 0.0;
                 const double lij = !keep ? 0.0 : (lane == j ? ljj : (lane > j ? A[j] / ljj : 0.0));
                 A[j] = lij;
@@ -337,23 +361,28 @@ __global__ __launch_bounds__(PSH_HMC_THREADS) void hmc_kernel(HmcArgs a) {
         isd1 = isd0;
     }
 
-    // ---- V_0 = gamma_0 (u = 0 at n = 0); implied vol
+    // ---- V_0 = gamma_0 (u = 0 at n = 0); implied vol.  Lanes 0..ns-1 of wave 0 hold `ill`.
+    if (tid == 0 && g == 0 && ill && a.status) atomicOr(&a.status[b], PSH_HMC_STATUS_ILL_CONDITIONED);
     if (tid < ns) {
         double K = Kj[0];
         bool call = callj[0];
 #pragma unroll
         for (int s = 1; s < SG; ++s)
             if (s == tid) { K = Kj[s]; call = callj[s]; }
-        const double price = coef[tid * NB];
+        const double price = ill ? NAN : coef[tid * NB];
         a.price[obase + tid] = price;
         a.strike[obase + tid] = K;
-        a.iv[obase + tid] = implied_vol(price, x0, K, tau, a.rate, call);
+        a.iv[obase + tid] = ill ? NAN : implied_vol(price, x0, K, tau, a.rate, call);
     }
 }
 
 hipError_t launch_hedged_mc(const HmcArgs& a, hipStream_t s) {
     const size_t shmem = (size_t)a.k * sizeof(double);
     const dim3 grid((unsigned)((int64_t)a.B * a.nT * a.ngroups)), block(PSH_HMC_THREADS);
+    if (a.status) {                                          // the blocks OR their bits in
+        const hipError_t e = hipMemsetAsync(a.status, 0, (size_t)a.B * sizeof(int32_t), s);
+        if (e != hipSuccess) return e;
+    }
 #define PSH_HMC_CASE(P)                                                                                          \
     case P: {                                                                                                    \
         hipError_t e = hipFuncSetAttribute((const void*)hmc_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize, \

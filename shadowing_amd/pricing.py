@@ -16,8 +16,10 @@ import numpy as np
 import torch
 
 KINDS = {"otm": 0, "call": 1, "put": 2}
-STATUS_OK, STATUS_NONFINITE, STATUS_WEIGHTS = 0, 1, 2
+STATUS_OK, STATUS_NONFINITE, STATUS_WEIGHTS, STATUS_ILL_CONDITIONED = 0, 1, 2, 4
 MAX_DEGREE = 5
+TAU_ILL = 0.2          # beta_0 kept at a step n > 0 with a pivot below TAU_ILL * its diagonal: ill-conditioned
+TAU_SING = 1e-6       # any unknown kept with a pivot below TAU_SING * its diagonal: ill-conditioned
 
 
 class PriceData:
@@ -125,17 +127,22 @@ def implied_vol(price: float, x0: float, K: float, tau: float, rate: float, call
     return 0.5 * (lo + hi)
 
 
-def _solve_dropping(G: np.ndarray, H: np.ndarray) -> np.ndarray:
-    """theta (NF, nM) of G theta = H by Cholesky in the fixed order of the unknowns; an unknown whose pivot is <= 1e-10
-    times its diagonal (or whose diagonal is 0) is dropped: theta = 0, its row and column removed."""
+def _solve_dropping(G: np.ndarray, H: np.ndarray, first_step: bool) -> tuple[np.ndarray, bool]:
+    """(theta (NF, nM), ill) of G theta = H by Cholesky in the fixed order of the unknowns; an unknown whose pivot is
+    <= 1e-10 times its diagonal (or whose diagonal is 0) is dropped: theta = 0, its row and column removed.  ill: an
+    unknown is kept with a pivot below TAU_SING times its diagonal, or (not at the first step, n = 0) beta_0 (unknown
+    NF / 2) is kept with a pivot below TAU_ILL times its diagonal."""
     nf = G.shape[0]
     L = np.zeros_like(G)
+    ill = False
     for j in range(nf):
         d = G[j, j]
         for c in range(j):
             d -= L[j, c] * L[j, c]
         if not (G[j, j] > 0.0 and d > 1e-10 * G[j, j]):
             continue                                          # dropped: column j of L stays 0
+        if d < TAU_SING * G[j, j] or (j == nf // 2 and not first_step and d < TAU_ILL * G[j, j]):
+            ill = True
         ljj = math.sqrt(d)
         L[j, j] = ljj
         for i in range(j + 1, nf):
@@ -154,7 +161,7 @@ def _solve_dropping(G: np.ndarray, H: np.ndarray) -> np.ndarray:
         for c in range(j + 1, nf):
             t -= L[c, j] * z[c]
         z[j] = t / L[j, j] if L[j, j] > 0.0 else 0.0
-    return z
+    return z, ill
 
 
 def _hmc_date(r: np.ndarray, w: np.ndarray | None, x0: float, rate: float, Ts, Ms, degree: int, kind: int):
@@ -196,7 +203,7 @@ def _hmc_date(r: np.ndarray, w: np.ndarray | None, x0: float, rate: float, Ts, M
         S[:, 0] = x0
         S1 = S[:, T]
         V = np.where(call[None, :], np.maximum(S1[:, None] - K[None, :], 0.0), np.maximum(K[None, :] - S1[:, None], 0.0))
-        gamma = None
+        gamma, ill = None, False
         for n in range(T - 1, -1, -1):
             S0, S1 = S[:, n], S[:, n + 1]
             mu, isd = x0, 0.0
@@ -221,12 +228,16 @@ def _hmc_date(r: np.ndarray, w: np.ndarray | None, x0: float, rate: float, Ts, M
             a = np.arange(NB)
             G = np.block([[mom[0][a[:, None] + a[None, :]], mom[1][a[:, None] + a[None, :]]],
                           [mom[1][a[:, None] + a[None, :]], mom[2][a[:, None] + a[None, :]]]])
-            gamma = _solve_dropping(G, H)[:NB]                          # (NB, nM)
+            theta, ill_n = _solve_dropping(G, H, n == 0)
+            gamma, ill = theta[:NB], ill or ill_n                     # gamma (NB, nM)
             V = np.broadcast_to(gamma[P], (u0.shape[0], nM)).copy()
             for c in range(P - 1, -1, -1):
                 V = V * u0[:, None] + gamma[c]
-        price[q] = gamma[0]
         strike[q] = K
+        if ill:                                                         # price and iv stay NaN
+            status |= STATUS_ILL_CONDITIONED
+            continue
+        price[q] = gamma[0]
         iv[q] = [implied_vol(float(price[q, j]), x0, float(K[j]), tau, rate, bool(call[j])) for j in range(nM)]
     return price, iv, strike, sigma_out, status
 

@@ -191,3 +191,136 @@ def test_smile_from_paths_host_and_argument_checks():
     imp = sa.PathShadowing(sa.Identity(20), sa.RelativeMSE(), ds, sa.ImputationContext(portion=(5, 10, 5)))
     with pytest.raises(NotImplementedError):
         imp.smile_from_paths(d, paths, [5], [0.0])
+
+
+# ---- known answers that neither implementation produced
+A, MS = ref.A, ref.MS
+@pytest.mark.parametrize("rate", [0.0, 0.05, -0.02])
+@pytest.mark.parametrize("kind", ["otm", "call", "put"])
+@pytest.mark.parametrize("P", [1, 2, 3, 4, 5])
+def test_binomial_tree_is_crr(P, kind, rate):
+    """T <= P + 1: the fit is exact at every step, so the price is the discounted CRR price whatever the weights."""
+    x0 = 100.0
+    for T in range(1, P + 2):
+        for reps, zero_half in [(3, False), (2, True), (16384 >> T, T % 2 == 0)]:
+            r, w, K, sig, crr = ref.binomial_case(P, T, reps, rate, kind, 1000 * P + 10 * T + reps, zero_half)
+            h = pricing.hedged_mc_host(r[None], w[None], [T], MS, x0, rate, P, pricing.KINDS[kind])
+            assert h["status"][0] == 0
+            np.testing.assert_allclose(h["sigma"][0], [sig], rtol=1e-14)
+            np.testing.assert_allclose(h["strike"][0, 0], K, rtol=1e-14)
+            np.testing.assert_allclose(h["price"][0, 0], crr, rtol=0, atol=1e-12 * x0)
+            if reps <= 3 or (P == 5 and T == 6):               # the restatement: small trees, and the one at k = 16384
+                rf = ref.hmc_date(r, w, x0, rate, [T], MS, P, kind)
+                assert rf["status"] == 0
+                np.testing.assert_allclose(rf["sigma"], [sig], rtol=1e-14)
+                np.testing.assert_allclose(rf["strike"][0], K, rtol=1e-14)
+                np.testing.assert_allclose(rf["price"][0], crr, rtol=0, atol=1e-12 * x0)
+
+
+def test_binomial_tree_beyond_p_plus_1_is_not_exact():
+    """The exactness above is a property of T <= P + 1 and not of the tree: one step more and the fit misses CRR."""
+    r, w, K, _, crr = ref.binomial_case(3, 5, 4, 0.05, "otm", 7)
+    h = pricing.hedged_mc_host(r[None], w[None], [5], MS, 100.0, 0.05, 3, 0)
+    assert np.max(np.abs(h["price"][0, 0] - crr)) > 1e-4
+
+
+@pytest.mark.parametrize("rate", [0.0, 0.04])
+@pytest.mark.parametrize("P", [1, 3, 5])
+def test_deterministic_paths_price_the_discounted_payoff(P, rate):
+    """k copies of one path, or one path with all the weight: u = 0 at every step (the basis is {1}) and beta_0 is
+    dropped, so the price is e^{-rho T} payoff(S_T)."""
+    x0, Ts = 100.0, [1, 4, 9]
+    g = np.random.default_rng(P)
+    path = (0.01 * g.standard_normal(9)).astype(np.float32)
+    copies = np.tile(path, (64, 1))
+    other = (0.01 * g.standard_normal((64, 9))).astype(np.float32)
+    other[17] = path
+    w1 = np.zeros(64)
+    w1[17] = 0.3
+    for r, w in [(copies, None), (copies, g.uniform(0.1, 1.0, 64)), (other, w1)]:
+        for kind in ["otm", "call", "put"]:
+            h = pricing.hedged_mc_host(r[None], None if w is None else w[None], Ts, MS, x0, rate, P, pricing.KINDS[kind])
+            rf = ref.hmc_date(r, w, x0, rate, Ts, MS, P, kind)
+            assert h["status"][0] == 0 and rf["status"] == 0
+            for q, T in enumerate(Ts):
+                ST = x0 * math.exp(float(np.sum(path[:T].astype(np.float64))))
+                K = h["strike"][0, q]
+                call = np.array([kind == "call" or (kind == "otm" and M >= 0) for M in MS])
+                want = math.exp(-rate * T / 252.0) * np.where(call, np.maximum(ST - K, 0.0), np.maximum(K - ST, 0.0))
+                np.testing.assert_allclose(h["price"][0, q], want, rtol=1e-13, atol=1e-13 * x0)
+                np.testing.assert_allclose(rf["price"][q], want, rtol=1e-13, atol=1e-13 * x0)
+
+
+@pytest.mark.parametrize("rate", [0.0, 0.03, -0.02])
+def test_all_zero_returns(rate):
+    """sigma = 0, every strike is the forward, and the IV is NaN wherever the price is below BS(1e-4)."""
+    x0, Ts = 100.0, [1, 5]
+    r = np.zeros((32, 5), dtype=np.float32)
+    for kind in ["call", "put"]:
+        h = pricing.hedged_mc_host(r[None], None, Ts, MS, x0, rate, 3, pricing.KINDS[kind])
+        rf = ref.hmc_date(r, None, x0, rate, Ts, MS, 3, kind)
+        assert h["status"][0] == 0 and rf["status"] == 0
+        assert np.all(h["sigma"][0] == 0.0) and np.all(rf["sigma"] == 0.0)
+        for q, T in enumerate(Ts):
+            tau = T / 252.0
+            F = x0 * math.exp(rate * tau)
+            np.testing.assert_allclose(h["strike"][0, q], F, rtol=1e-15)
+            want = math.exp(-rate * tau) * (max(x0 - F, 0.0) if kind == "call" else max(F - x0, 0.0))
+            np.testing.assert_allclose(h["price"][0, q], want, rtol=1e-13, atol=1e-13 * x0)
+            np.testing.assert_allclose(rf["price"][q], want, rtol=1e-13, atol=1e-13 * x0)
+            lo = ref.bs(x0, F, tau, rate, 1e-4, kind == "call")
+            if want < lo:
+                assert np.isnan(h["iv"][0, q]).all() and np.isnan(rf["iv"][q]).all()
+            else:                              # (a put when rate > 0: the paths lag the forward)
+                iv = ref.implied_vol(want, x0, F, tau, rate, kind == "call")
+                assert np.isfinite(iv)
+                np.testing.assert_allclose(h["iv"][0, q], iv, rtol=0, atol=1e-8)
+
+
+@pytest.mark.parametrize("P", [1, 2, 3, 4, 5])
+def test_put_call_parity_of_prices(P):
+    """C - P = x0 - K e^{-rate tau} for any paths and weights: S_T - K is fitted exactly at every step."""
+    rng = np.random.default_rng(50 + P)
+    r = gbm_returns(rng, 500, 20, 0.3, rate=0.03)
+    w = rng.random(500)
+    Ts, Ms, x0 = [1, 7, 20], np.linspace(-2, 2, 9), 100.0
+    c = pricing.hedged_mc_host(r[None], w[None], Ts, Ms, x0, 0.03, P, pricing.KINDS["call"])
+    p = pricing.hedged_mc_host(r[None], w[None], Ts, Ms, x0, 0.03, P, pricing.KINDS["put"])
+    tau = (np.asarray(Ts) / 252.0)[:, None]
+    np.testing.assert_allclose(c["price"][0] - p["price"][0], x0 - c["strike"][0] * np.exp(-0.03 * tau), rtol=0,
+                               atol=1e-10 * x0)
+    rc = ref.hmc_date(r, w, x0, 0.03, Ts, Ms[[0, 4, 8]], P, "call")
+    rp = ref.hmc_date(r, w, x0, 0.03, Ts, Ms[[0, 4, 8]], P, "put")
+    np.testing.assert_allclose(rc["price"] - rp["price"], x0 - rc["strike"] * np.exp(-0.03 * tau), rtol=0, atol=1e-10 * x0)
+
+
+# ---- the ill-conditioned regime: a common drift and little spread between the paths
+@pytest.mark.parametrize("P", [1, 3, 5])
+@pytest.mark.parametrize("c", [0.0, 0.001, -0.001, 0.003, 0.01])
+def test_drift_sweep_flags_or_agrees(c, P):
+    Ts, Ms = [5, 20], [-1.0, 0.0, 1.0]
+    flagged = []
+    for e in ref.SWEEP_E:
+        r, w = ref.drift_returns(c, e)
+        h = pricing.hedged_mc_host(r[None], w[None], Ts, Ms, 100.0, 0.0, P, 0)
+        rf = ref.hmc_date(r, w, 100.0, 0.0, Ts, Ms, P, "otm")
+        nan = ref.check_sweep_case({k: v[0] for k, v in h.items()}, rf, Ts, Ms)
+        flagged.append(bool(nan.any()))
+    if c == 0.0:
+        assert not any(flagged)                                           # no drift: the hedge is never riskless
+    if abs(c) >= 0.003:
+        assert flagged[-1] and flagged[-2]                                 # |c| >= 300 e
+
+
+@pytest.mark.parametrize("P,seed", [(5, 2), (4, 0), (3, 1)])
+def test_student_t_flags_or_agrees(P, seed):
+    """Heavy tails at T = 75: dates whose fit a few outlying paths make nearly singular are flagged (any kept pivot below
+    TAU_SING); the others agree with the restatement to 1e-9."""
+    Ts, Ms = [10, 40, 75], [-1.0, 0.0, 1.0]
+    r, w = ref.student_t_dates(seed)
+    h = pricing.hedged_mc_host(r, w, Ts, Ms, 100.0, 0.01, P, 0)
+    flagged = 0
+    for b in range(r.shape[0]):
+        rf = ref.hmc_date(r[b], w[b], 100.0, 0.01, Ts, Ms, P, "otm")
+        flagged += bool(ref.check_sweep_case({k: v[b] for k, v in h.items()}, rf, Ts, Ms).any())
+    assert 1 <= flagged < r.shape[0]                                  # some flagged, some priced
