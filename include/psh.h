@@ -532,6 +532,28 @@ int psh_hedged_mc(int device, void* stream, const float* dlnx, int64_t row_strid
                   int degree, int kind, double* out_price, double* out_iv, double* out_strike, double* out_sigma,
                   int32_t* out_status);
 
+/*
+ * Path generation of the discrete path-dependent volatility model (Guyon, Lekeufack 2024): S paths of n_steps steps for
+ * each of B dates, one lane per path, in double.  The method, in full, heads shadowing_amd/csrc/psh_pdv.hip (and README
+ * "PDV model"); shadowing_amd/pdv.py (PDVModelDiscrete.gen, pdv_future_paths) is its numpy twin.
+ *   lams1, lams2, decay1, decay2, thetas: HOST arrays of 2 (decay = exp(-lams / 252) as the caller computed it);
+ *   betas: HOST array of n_betas = 3 or 4;  S0: the first price of every path;  sqrt_dt: the scale of the draws;
+ *   nu: 0 for Gaussian draws, > 0 for Student-t(nu) draws (unused when draws != NULL);
+ *   R10, R20: device B x 2 float64, the initial factors of each date;
+ *   draws: device (B*S) x n_steps float64 raw draws (normalised here), or NULL: Philox4x32-10 keyed by `seed`, the draws
+ *          of path g = b * S + p at step t depending only on (seed, g, t);
+ *   out_sigma, out_St: device (B*S) x n_steps float64;  out_dlnx: device (B*S) x (n_steps - 1) float32 log1p of the
+ *   returns (the layout psh_hedged_mc reads);  out_draws, out_dw: device (B*S) x n_steps float64 raw and normalised
+ *   draws.  Each output may be NULL.
+ * A NULL input, B < 1, S < 1, n_steps < 1, n_betas not 3 or 4, nu < 0 or not finite, or B * S * n_steps past int64:
+ * PSH_ERR_ARG before anything touches the device; B * S >= 2^39: PSH_ERR_UNSUPPORTED.  Two calls give identical bits.
+ */
+int psh_pdv_generate(int device, void* stream, int B, int64_t S, int n_steps, const double* lams1, const double* lams2,
+                     const double* decay1, const double* decay2, const double* thetas, const double* betas, int n_betas,
+                     double S0, double sqrt_dt, double nu, const double* R10, const double* R20, const double* draws,
+                     uint64_t seed, double* out_sigma, double* out_St, float* out_dlnx, double* out_draws,
+                     double* out_dw);
+
 #ifdef __cplusplus
 }
 #endif

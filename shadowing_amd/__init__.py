@@ -11,6 +11,7 @@ from .path_embedding import (ArrayType, ContextManagerBase, CrossChannelContext,
                              ImputationContext, PathEmbedding, PredictionContext)
 from .path_shadowing import PathShadowing, PendingShadow, select_cartesian_product
 from .plotting import plot_closest, plot_shadow, plot_volatility
+from .pdv import AutoregressiveLinearPredictor, PDVModel, PDVModelDiscrete
 from .pricing import PriceData, Smile, compute_smile
 from .statistics import realized_variance
 
@@ -19,5 +20,6 @@ __all__ = [
     "PathEmbedding", "Identity", "Foveal", "PathDistance", "RelativeMSE", "PathShadowing",
     "select_cartesian_product", "DiscreteProba", "Softmax", "Uniform", "realized_variance",
     "plot_closest", "plot_shadow", "plot_volatility", "PriceData", "Smile", "compute_smile",
+    "PDVModel", "PDVModelDiscrete", "AutoregressiveLinearPredictor",
 ]
 __version__ = "0.1.0"

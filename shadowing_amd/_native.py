@@ -48,7 +48,7 @@ EXPORTS = ("psh_version", "psh_strerror", "psh_last_hip_error", "psh_workspace_b
            "psh_embedded_supported", "psh_embed_plan_offset", "psh_candidates_layout", "psh_workspace_init", "psh_last_comm_error", "psh_comm_unique_id", "psh_comm_create",
            "psh_comm_destroy", "psh_comm_world", "psh_exchange_merge", "psh_stream_create_reserving", "psh_stream_destroy",
            "psh_weighted_moments", "psh_realized_variance", "psh_count_nonfinite", "psh_smear_nonfinite", "psh_rows_nonfinite",
-           "psh_shadow_block_layout", "psh_shadow_blocking", "psh_hedged_mc")
+           "psh_shadow_block_layout", "psh_shadow_blocking", "psh_hedged_mc", "psh_pdv_generate")
 
 _lib = None
 
@@ -151,6 +151,10 @@ def load() -> C.CDLL:
     L.psh_hedged_mc.restype = i32
     L.psh_hedged_mc.argtypes = [i32, vp, vp, i64, i32, i32, i32, vp, C.c_double, C.c_double, C.POINTER(C.c_int), i32,
                                 C.POINTER(C.c_double), i32, i32, i32, vp, vp, vp, vp, vp]
+    L.psh_pdv_generate.restype = i32
+    L.psh_pdv_generate.argtypes = [i32, vp, i32, i64, i32] + [C.POINTER(C.c_double)] * 6 + [i32, C.c_double, C.c_double,
+                                                                                          C.c_double, vp, vp, vp, C.c_uint64,
+                                                                                          vp, vp, vp, vp, vp]
     L.psh_gather_paths.restype = i32
     L.psh_gather_paths.argtypes = [i32, vp, vp, i64, i64, i64, i64, vp, i64, i32, vp]
     if L.psh_version() != PSH_VERSION:
@@ -986,6 +990,49 @@ def hedged_mc(dlnx: torch.Tensor, weights: torch.Tensor | None, Ts, Ms, x_init: 
                                 (C.c_double * max(nM, 1))(*Ms), nM, int(degree), int(kind), out["price"].data_ptr(),
                                 out["iv"].data_ptr(), out["strike"].data_ptr(), out["sigma"].data_ptr(),
                                 out["status"].data_ptr()), "psh_hedged_mc")
+    return out
+
+
+PDV_OUTPUTS = ("sigma", "St", "dlnx", "raw", "dw")
+
+
+def pdv_generate(B: int, S: int, n_steps: int, lams1, lams2, decay1, decay2, thetas, betas, S0: float, sqrt_dt: float,
+                 nu: float, R10, R20, *, draws: torch.Tensor | None = None, seed: int = 0, outputs=("sigma", "St"),
+                 device: torch.device | None = None) -> dict:
+    """psh_pdv_generate: S paths of n_steps steps for each of B dates of the discrete PDV model (shadowing_amd/pdv.py).
+    lams1 .. thetas: 2 values each, betas: 3 or 4; R10, R20: (B, 2) initial factors (numpy or tensors); draws: (B*S,
+    n_steps) float64 device tensor of raw draws, or None: the counter-based generator keyed by `seed`.  Returns a dict of
+    the requested `outputs` (of PDV_OUTPUTS) as device tensors: (B*S, n_steps) float64, "dlnx" (B*S, n_steps - 1)
+    float32.  Nothing is synchronised."""
+    bad = [o for o in outputs if o not in PDV_OUTPUTS]
+    if bad:
+        raise ValueError(f"unknown outputs {bad}; choose from {PDV_OUTPUTS}")
+    if draws is not None:
+        draws = _dev_tensor(draws, torch.float64, "draws")
+        if tuple(draws.shape) != (B * S, n_steps):
+            raise ValueError(f"draws must be ({B * S}, {n_steps}), got {tuple(draws.shape)}")
+    dev = draws.device if draws is not None else (device or torch.device("cuda", torch.cuda.current_device()))
+    r10, r20 = (torch.as_tensor(R, dtype=torch.float64).to(dev).reshape(B, 2).contiguous() for R in (R10, R20))
+
+    def host(v, n):
+        v = [float(x) for x in v]
+        if len(v) != n:
+            raise ValueError(f"expected {n} values, got {len(v)}")
+        return (C.c_double * n)(*v)
+
+    nb = len(betas)
+    if nb not in (3, 4):
+        raise ValueError(f"betas must hold 3 or 4 values, got {nb}")
+    out = {}
+    for name in outputs:
+        shape, dtype = ((B * S, n_steps - 1), torch.float32) if name == "dlnx" else ((B * S, n_steps), torch.float64)
+        out[name] = torch.empty(shape, dtype=dtype, device=dev)
+    ptr = lambda name: out[name].data_ptr() if name in out else None   # noqa: E731
+    _check(load().psh_pdv_generate(dev.index, _stream_ptr(dev), int(B), int(S), int(n_steps), host(lams1, 2), host(lams2, 2),
+                                   host(decay1, 2), host(decay2, 2), host(thetas, 2), host(betas, nb), nb, float(S0),
+                                   float(sqrt_dt), float(nu), r10.data_ptr(), r20.data_ptr(),
+                                   None if draws is None else draws.data_ptr(), int(seed), ptr("sigma"), ptr("St"),
+                                   ptr("dlnx"), ptr("raw"), ptr("dw")), "psh_pdv_generate")
     return out
 
 

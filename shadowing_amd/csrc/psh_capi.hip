@@ -1473,4 +1473,31 @@ int psh_hedged_mc(int device, void* stream, const float* dlnx, int64_t row_strid
     return PSH_OK;
 }
 
+int psh_pdv_generate(int device, void* stream, int B, int64_t S, int n_steps, const double* lams1, const double* lams2,
+                     const double* decay1, const double* decay2, const double* thetas, const double* betas, int n_betas,
+                     double S0, double sqrt_dt, double nu, const double* R10, const double* R20, const double* draws,
+                     uint64_t seed, double* out_sigma, double* out_St, float* out_dlnx, double* out_draws,
+                     double* out_dw) {
+    if (!lams1 || !lams2 || !decay1 || !decay2 || !thetas || !betas || !R10 || !R20 || B < 1 || S < 1 || n_steps < 1 ||
+        (n_betas != 3 && n_betas != 4) || !std::isfinite(nu) || nu < 0.0)
+        return PSH_ERR_ARG;
+    if (S > INT64_MAX / B || (int64_t)B * S > INT64_MAX / n_steps) return PSH_ERR_ARG;
+    if ((int64_t)B * S >= ((int64_t)1 << 39)) return PSH_ERR_UNSUPPORTED;   // (the grid is B * S / 256 blocks)
+    PdvArgs a{};
+    a.n_paths = (int64_t)B * S; a.S = S; a.n = n_steps; a.n_betas = n_betas;
+    for (int i = 0; i < 2; ++i) {
+        a.lam1[i] = lams1[i]; a.lam2[i] = lams2[i]; a.decay1[i] = decay1[i]; a.decay2[i] = decay2[i];
+        a.theta[i] = thetas[i];
+    }
+    for (int i = 0; i < n_betas; ++i) a.beta[i] = betas[i];
+    a.S0 = S0; a.sqdt = sqrt_dt; a.nu = nu; a.nexp = nu > 0.0 ? -2.0 / nu : 0.0;
+    a.key0 = (uint32_t)seed; a.key1 = (uint32_t)(seed >> 32);
+    a.R10 = R10; a.R20 = R20; a.draws = draws;
+    a.sigma = out_sigma; a.St = out_St; a.dlnx = out_dlnx; a.raw = out_draws; a.dw = out_dw;
+    DeviceGuard g(device);
+    if (!g.ok) { snprintf(g_hip_err, sizeof(g_hip_err), "hipSetDevice(%d) failed", device); return PSH_ERR_HIP; }
+    HIP_TRY(launch_pdv(a, (hipStream_t)stream));
+    return PSH_OK;
+}
+
 }  // extern "C"

@@ -401,4 +401,22 @@ struct HmcArgs {
 };
 hipError_t launch_hedged_mc(const HmcArgs& a, hipStream_t s);
 
+// psh_pdv.hip: path generation of the discrete PDV model (psh_pdv_generate)
+struct PdvArgs {
+    int64_t n_paths, S;       // B * S paths, S per date
+    int n, n_betas;           // steps; 3 or 4 betas
+    double lam1[2], lam2[2], decay1[2], decay2[2], theta[2], beta[4];
+    double S0, sqdt, nu, nexp;   // nu = 0: Gaussian draws; nexp = -2 / nu
+    uint32_t key0, key1;      // the seed's low and high words
+    const double* R10;        // (B, 2) initial factors
+    const double* R20;
+    const double* draws;      // (n_paths, n) raw draws, or nullptr: Philox
+    double* sigma;            // (n_paths, n) or nullptr, as every output
+    double* St;
+    float* dlnx;              // (n_paths, n - 1)
+    double* raw;              // (n_paths, n)
+    double* dw;               // (n_paths, n)
+};
+hipError_t launch_pdv(const PdvArgs& a, hipStream_t s);
+
 }  // namespace psh
