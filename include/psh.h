@@ -554,6 +554,28 @@ int psh_pdv_generate(int device, void* stream, int B, int64_t S, int n_steps, co
                      uint64_t seed, double* out_sigma, double* out_St, float* out_dlnx, double* out_draws,
                      double* out_dw);
 
+/*
+ * An ensemble of R log-normal multifractal random walks (Bacry, Delour, Muzy 2001) of n returns each, made on the
+ * device: r[t] = sigma * eps[t] * exp(omega[t] - c0), omega Gaussian with the log-correlated covariance c, eps
+ * fractional Gaussian noise (white for H = 0.5), both by circulant embedding, one workgroup and one in-LDS transform per
+ * pair of paths, in double.  The method, in full, heads shadowing_amd/csrc/psh_mrw.hip (and README "MRW ensemble");
+ * shadowing_amd/mrw.py (mrw_log_returns, MRWGenerator) is its numpy twin and computes the tables.
+ *   M: the smallest power of two >= 2n;
+ *   a_omega: device M float64, sqrt(max(s[k], 0) / M) with s the eigenvalues of omega's circulant covariance;
+ *   a_eps: the same table for fractional Gaussian noise, or NULL: H = 0.5, eps is white noise drawn directly;
+ *   c0: c[0] = Var omega, so that E[r^2] = sigma^2;  seed: the Philox4x32-10 key -- the samples of path g depend only on
+ *   (seed, g, n, the tables), never on R;
+ *   out_dlnx: device float32, row g at out_dlnx + g * dlnx_row_stride (n floats; the bytes between rows are left alone),
+ *   so a (R, 1, n) ensemble is written where the scan reads it;  out_lnx: device R x (n + 1) float64 log-prices from 0;
+ *   out_omega: device R x n float64.  Each output may be NULL.
+ * A NULL a_omega, R < 1, n < 2, sigma < 0 or not finite, c0 not finite, or dlnx_row_stride < n with out_dlnx:
+ * PSH_ERR_ARG before anything touches the device; n > 4096 (the transform leaves LDS) or R >= 2^32:
+ * PSH_ERR_UNSUPPORTED.  Two calls give identical bits.
+ */
+int psh_mrw_generate(int device, void* stream, int64_t R, int n, double sigma, const double* a_omega, const double* a_eps,
+                     double c0, uint64_t seed, float* out_dlnx, int64_t dlnx_row_stride, double* out_lnx,
+                     double* out_omega);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,7 +48,7 @@ EXPORTS = ("psh_version", "psh_strerror", "psh_last_hip_error", "psh_workspace_b
            "psh_embedded_supported", "psh_embed_plan_offset", "psh_candidates_layout", "psh_workspace_init", "psh_last_comm_error", "psh_comm_unique_id", "psh_comm_create",
            "psh_comm_destroy", "psh_comm_world", "psh_exchange_merge", "psh_stream_create_reserving", "psh_stream_destroy",
            "psh_weighted_moments", "psh_realized_variance", "psh_count_nonfinite", "psh_smear_nonfinite", "psh_rows_nonfinite",
-           "psh_shadow_block_layout", "psh_shadow_blocking", "psh_hedged_mc", "psh_pdv_generate")
+           "psh_shadow_block_layout", "psh_shadow_blocking", "psh_hedged_mc", "psh_pdv_generate", "psh_mrw_generate")
 
 _lib = None
 
@@ -155,6 +155,8 @@ def load() -> C.CDLL:
     L.psh_pdv_generate.argtypes = [i32, vp, i32, i64, i32] + [C.POINTER(C.c_double)] * 6 + [i32, C.c_double, C.c_double,
                                                                                           C.c_double, vp, vp, vp, C.c_uint64,
                                                                                           vp, vp, vp, vp, vp]
+    L.psh_mrw_generate.restype = i32
+    L.psh_mrw_generate.argtypes = [i32, vp, i64, i32, C.c_double, vp, vp, C.c_double, C.c_uint64, vp, i64, vp, vp]
     L.psh_gather_paths.restype = i32
     L.psh_gather_paths.argtypes = [i32, vp, vp, i64, i64, i64, i64, vp, i64, i32, vp]
     if L.psh_version() != PSH_VERSION:
@@ -1033,6 +1035,54 @@ def pdv_generate(B: int, S: int, n_steps: int, lams1, lams2, decay1, decay2, the
                                    float(sqrt_dt), float(nu), r10.data_ptr(), r20.data_ptr(),
                                    None if draws is None else draws.data_ptr(), int(seed), ptr("sigma"), ptr("St"),
                                    ptr("dlnx"), ptr("raw"), ptr("dw")), "psh_pdv_generate")
+    return out
+
+
+MRW_OUTPUTS = ("dlnx", "lnx", "omega")
+PSH_MRW_MAX_N = 4096
+
+
+def mrw_generate(R: int, n: int, sigma: float, a_omega: torch.Tensor, a_eps: torch.Tensor | None, c0: float, *,
+                 seed: int = 0, outputs=("dlnx",), dlnx_out: torch.Tensor | None = None) -> dict:
+    """psh_mrw_generate: R multifractal random walks of n returns (shadowing_amd/mrw.py computes the tables).  a_omega,
+    a_eps: (M,) float64 device tensors, M the smallest power of two >= 2n (a_eps None: H = 0.5).  Returns a dict of the
+    requested `outputs` (of MRW_OUTPUTS) as device tensors: "dlnx" (R, 1, n) float32, "lnx" (R, n + 1) and "omega" (R, n)
+    float64.  dlnx_out: a float32 device tensor (R, ..) whose rows (stride(0) >= n floats apart, unit stride inside) take
+    the returns instead of a fresh tensor; whatever lies between the rows is left alone.  Nothing is synchronised."""
+    bad = [o for o in outputs if o not in MRW_OUTPUTS]
+    if bad:
+        raise ValueError(f"unknown outputs {bad}; choose from {MRW_OUTPUTS}")
+    if n > PSH_MRW_MAX_N:
+        raise ValueError(f"psh_mrw_generate makes paths of n <= {PSH_MRW_MAX_N} returns, got {n}")
+    M = 4
+    while M < 2 * n:
+        M *= 2
+    a_omega = _dev_tensor(a_omega, torch.float64, "a_omega")
+    dev = a_omega.device
+    if a_eps is not None:
+        a_eps = _dev_tensor(a_eps, torch.float64, "a_eps")
+    for name, t in (("a_omega", a_omega), ("a_eps", a_eps)):
+        if t is not None and (tuple(t.shape) != (M,) or t.device != dev):
+            raise ValueError(f"{name} must hold M = {M} values on {dev}, got {tuple(t.shape)} on {t.device}")
+    out = {}
+    stride = n
+    if "dlnx" in outputs:
+        if dlnx_out is not None:
+            if (not isinstance(dlnx_out, torch.Tensor) or dlnx_out.device != dev or dlnx_out.dtype != torch.float32 or
+                    dlnx_out.dim() < 2 or dlnx_out.shape[0] != R or dlnx_out.shape[-1] < n or dlnx_out.stride(-1) != 1 or
+                    (R > 1 and dlnx_out.stride(0) < n)):
+                raise ValueError(f"dlnx_out must be a float32 tensor on {dev} with {R} rows of >= {n} contiguous floats")
+            out["dlnx"], stride = dlnx_out, (dlnx_out.stride(0) if R > 1 else n)
+        else:
+            out["dlnx"] = torch.empty((R, 1, n), dtype=torch.float32, device=dev)
+    if "lnx" in outputs:
+        out["lnx"] = torch.empty((R, n + 1), dtype=torch.float64, device=dev)
+    if "omega" in outputs:
+        out["omega"] = torch.empty((R, n), dtype=torch.float64, device=dev)
+    ptr = lambda name: out[name].data_ptr() if name in out else None   # noqa: E731
+    _check(load().psh_mrw_generate(dev.index, _stream_ptr(dev), int(R), int(n), float(sigma), a_omega.data_ptr(),
+                                   None if a_eps is None else a_eps.data_ptr(), float(c0), int(seed), ptr("dlnx"),
+                                   int(stride), ptr("lnx"), ptr("omega")), "psh_mrw_generate")
     return out
 
 

@@ -1500,4 +1500,24 @@ int psh_pdv_generate(int device, void* stream, int B, int64_t S, int n_steps, co
     return PSH_OK;
 }
 
+int psh_mrw_generate(int device, void* stream, int64_t R, int n, double sigma, const double* a_omega, const double* a_eps,
+                     double c0, uint64_t seed, float* out_dlnx, int64_t dlnx_row_stride, double* out_lnx,
+                     double* out_omega) {
+    if (!a_omega || R < 1 || n < 2 || !std::isfinite(sigma) || sigma < 0.0 || !std::isfinite(c0) ||
+        (out_dlnx && dlnx_row_stride < n))
+        return PSH_ERR_ARG;
+    if (n > PSH_MRW_MAX_N || R >= ((int64_t)1 << 32)) return PSH_ERR_UNSUPPORTED;   // (the grid is R / 2 workgroups)
+    if (out_dlnx && R > INT64_MAX / dlnx_row_stride) return PSH_ERR_ARG;
+    MrwArgs a{};
+    a.R = R; a.n = n; a.logM = 2;
+    while ((1 << a.logM) < 2 * n) ++a.logM;
+    a.sigma = sigma; a.c0 = c0; a.key0 = (uint32_t)seed; a.key1 = (uint32_t)(seed >> 32);
+    a.a_omega = a_omega; a.a_eps = a_eps;
+    a.dlnx = out_dlnx; a.dlnx_stride = dlnx_row_stride; a.lnx = out_lnx; a.omega = out_omega;
+    DeviceGuard g(device);
+    if (!g.ok) { snprintf(g_hip_err, sizeof(g_hip_err), "hipSetDevice(%d) failed", device); return PSH_ERR_HIP; }
+    HIP_TRY(launch_mrw(a, (hipStream_t)stream));
+    return PSH_OK;
+}
+
 }  // extern "C"

@@ -419,4 +419,20 @@ struct PdvArgs {
 };
 hipError_t launch_pdv(const PdvArgs& a, hipStream_t s);
 
+// psh_mrw.hip: an ensemble of multifractal random walks (psh_mrw_generate)
+#define PSH_MRW_MAX_N 4096    // the transform of M = 2^logM >= 2n complex doubles stays in LDS: M <= 8192
+struct MrwArgs {
+    int64_t R;                // paths; workgroup q makes paths 2q and 2q + 1
+    int n, logM;              // returns per path; M = 2^logM is the smallest power of two >= 2n
+    double sigma, c0;         // r = sigma * eps * exp(omega - c0)
+    uint32_t key0, key1;      // the seed's low and high words
+    const double* a_omega;    // (M) sqrt(eigenvalue / M) of omega's circulant covariance
+    const double* a_eps;      // (M) the same for fractional Gaussian noise, or nullptr: white noise (H = 0.5)
+    float* dlnx;              // rows of n returns, dlnx_stride floats apart, or nullptr, as every output
+    int64_t dlnx_stride;
+    double* lnx;              // (R, n + 1)
+    double* omega;            // (R, n)
+};
+hipError_t launch_mrw(const MrwArgs& a, hipStream_t s);
+
 }  // namespace psh

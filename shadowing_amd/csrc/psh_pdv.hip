@@ -44,47 +44,21 @@
 
 #include "psh.h"
 #include "psh_kernels.h"
+#include "psh_philox.h"
 
 namespace psh {
 
 #define PSH_PDV_THREADS 256
 #define PSH_PDV_CH 8
 #define PSH_PDV_MAX_ATTEMPTS 64
-#define PSH_PDV_TWO_PI 6.283185307179586
 
 namespace {
 
 enum { PDV_GAUSS = 0, PDV_STUDENT = 1, PDV_GIVEN = 2 };
 
-// Random123's Philox4x32-10 (the round of rocrand_philox4x32_10.h)
-__device__ __forceinline__ void philox4x32_10(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3, uint32_t k0,
-                                              uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        if (r) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
-    }
-}
-
-// the two 53-bit words of one Philox call on counter (c0, c1, g lo, g hi)
-__device__ __forceinline__ void philox_words(uint32_t c0, uint32_t c1, uint64_t g, uint32_t k0, uint32_t k1, uint64_t& a,
-                                             uint64_t& b) {
-    uint32_t c2 = (uint32_t)g, c3 = (uint32_t)(g >> 32);
-    philox4x32_10(c0, c1, c2, c3, k0, k1);
-    a = ((((uint64_t)c1) << 32) | c0) >> 11;
-    b = ((((uint64_t)c3) << 32) | c2) >> 11;
-}
-
+// Philox4x32-10, its 53-bit words and Box-Muller: psh_philox.h (shared with psh_mrw.hip)
 __device__ __forceinline__ void normal_pair(uint32_t m, uint64_t g, uint32_t k0, uint32_t k1, double& z0, double& z1) {
-    uint64_t a, b;
-    philox_words(m, 0u, g, k0, k1, a, b);
-    const double u1 = (double)(a + 1) * 0x1p-53, u2 = (double)b * 0x1p-53;
-    const double rad = sqrt(-2.0 * log(u1));
-    const double ang = PSH_PDV_TWO_PI * u2;
-    z0 = rad * cos(ang);
-    z1 = rad * sin(ang);
+    philox_normal_pair(m, 0u, g, k0, k1, z0, z1);
 }
 
 __device__ __forceinline__ double student_t(uint32_t t, uint64_t g, uint32_t k0, uint32_t k1, double nu, double nexp) {

@@ -354,7 +354,7 @@ def _normalise(dw: np.ndarray, s: float) -> np.ndarray:
     return dw
 
 
-# ---- the counter-based generator (psh_pdv.hip states it; this is its numpy twin)
+# ---- the counter-based generator (psh_philox.h and psh_pdv.hip state it; this is its numpy twin, shared with mrw.py)
 _M0, _M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
 _LO32, _SH32, _SH11 = np.uint64(0xFFFFFFFF), np.uint64(32), np.uint64(11)
 
@@ -377,6 +377,18 @@ def _words(counter, key):
     return ((x1 << _SH32) | x0) >> _SH11, ((x3 << _SH32) | x2) >> _SH11
 
 
+def normal_pairs(counter, key):
+    """One Box-Muller pair (z0, z1) per counter (4 broadcast arrays of 32-bit values), as psh_philox.h states it:
+    u1 = (a + 1) 2^-53, u2 = b 2^-53 from the call's two 53-bit words, rad = sqrt(-2 ln u1), z0 = rad cos(2 pi u2),
+    z1 = rad sin(2 pi u2)."""
+    a, b = _words(counter, key)
+    u1 = (a + np.uint64(1)).astype(np.float64) * 2.0 ** -53
+    u2 = b.astype(np.float64) * 2.0 ** -53
+    rad = np.sqrt(-2.0 * np.log(u1))
+    ang = TWO_PI * u2
+    return rad * np.cos(ang), rad * np.sin(ang)
+
+
 def philox_draws(seed: int, n_paths: int, n_steps: int, nu: float = 0.0, first_path: int = 0) -> np.ndarray:
     """(n_paths, n_steps) raw draws of paths first_path.. of the counter-based generator: Gaussian (nu = 0) or
     Student-t(nu), exactly as psh_pdv.hip states them."""
@@ -388,14 +400,8 @@ def philox_draws(seed: int, n_paths: int, n_steps: int, nu: float = 0.0, first_p
         glo, ghi = g & _LO32, g >> _SH32
         if nu == 0.0:
             m = np.arange((n_steps + 1) // 2, dtype=np.uint64)[None, :]
-            a, b = _words((m, np.uint64(0), glo, ghi), key)
-            u1 = (a + np.uint64(1)).astype(np.float64) * 2.0 ** -53
-            u2 = b.astype(np.float64) * 2.0 ** -53
-            rad = np.sqrt(-2.0 * np.log(u1))
-            ang = TWO_PI * u2
             z = np.empty((g.shape[0], 2 * m.shape[1]))
-            z[:, 0::2] = rad * np.cos(ang)
-            z[:, 1::2] = rad * np.sin(ang)
+            z[:, 0::2], z[:, 1::2] = normal_pairs((m, np.uint64(0), glo, ghi), key)
             out[p0:p0 + g.shape[0]] = z[:, :n_steps]
             continue
         nexp = -2.0 / nu
@@ -467,4 +473,4 @@ def pdv_future_paths(x_past: np.ndarray, pdv_model: PDVModelDiscrete, w: int, S0
 
 __all__ = ["kernel_pl", "kernel_exp", "get_RV", "DEFAULT1", "DEFAULT2", "windows", "AutoregressiveLinearPredictor",
            "PDVModel", "PDVModelDiscrete", "compute_factor", "future_pdv_model", "pdv_future_paths", "philox4x32_10",
-           "philox_draws"]
+           "normal_pairs", "philox_draws"]
