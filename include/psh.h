@@ -576,6 +576,29 @@ int psh_mrw_generate(int device, void* stream, int64_t R, int n, double sigma, c
                      double c0, uint64_t seed, float* out_dlnx, int64_t dlnx_row_stride, double* out_lnx,
                      double* out_omega);
 
+/*
+ * An ensemble of R skewed multifractal random walks (Pochart, Bouchaud 2002) of n returns each: the MRW above with white
+ * noise and a leverage term in the log-volatility,
+ *   lv[t] = omega[t] - A[t],  A[t] = sum_{j=1..m} K(j) eps[t - j],  r[t] = sigma * eps[t] * exp(lv[t] - c0 - v),
+ * K(j) = K0 / j^alpha, v = sum_j K(j)^2, so E[r^2] = sigma^2 at every t and E[r_t r_{t+tau}^2] < 0 for K0 > 0.  The
+ * method, in full, heads shadowing_amd/csrc/psh_smrw.hip (and README "Skewed MRW"); shadowing_amd/mrw.py
+ * (smrw_log_returns, SMRWGenerator) is its numpy twin and computes the tables.
+ *   M, a_omega, c0, sigma, seed, out_dlnx, dlnx_row_stride, out_lnx: as psh_mrw_generate; omega and eps[t], t >= 0, are
+ *   that function's draws at H = 0.5, and the pre-history eps[-m .. -1] is drawn on a stream of its own;
+ *   m: the memory of the kernel in lags, 1 <= m <= M - n (the convolution is linear inside the circulant of size M);
+ *   k_hat: device M complex float64 (2 M doubles, re then im), k_hat[k] = conj(F[k]) exp(-2 pi i k m / M) / M with
+ *   F = FFT_M of (0, K(1), .., K(m), 0, ..): the index reversal, the shift by m and the 1 / M of the inverse transform
+ *   folded in, so that A = FFT_M(k_hat[k] X[(-k) mod M]) with X the transform of the noise.  All zeros is the MRW;
+ *   v: sum_j K(j)^2;  out_logvol: device R x n float64, lv = omega - A.  Each output may be NULL.
+ * A NULL a_omega or k_hat, R < 1, n < 2, m < 1, n + m > M, sigma < 0 or not finite, c0 or v not finite, or
+ * dlnx_row_stride < n with out_dlnx: PSH_ERR_ARG before anything touches the device; n > 4096 or R >= 2^32:
+ * PSH_ERR_UNSUPPORTED (and then m is not looked at).  Two calls give identical bits; a path depends only on
+ * (seed, path, n, m, the tables), never on R.
+ */
+int psh_smrw_generate(int device, void* stream, int64_t R, int n, int m, double sigma, const double* a_omega,
+                      const double* k_hat, double c0, double v, uint64_t seed, float* out_dlnx, int64_t dlnx_row_stride,
+                      double* out_lnx, double* out_logvol);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,7 @@ from .path_embedding import (ArrayType, ContextManagerBase, CrossChannelContext,
                              ImputationContext, PathEmbedding, PredictionContext)
 from .path_shadowing import PathShadowing, PendingShadow, select_cartesian_product
 from .plotting import plot_closest, plot_shadow, plot_volatility
-from .mrw import MRWGenerator, mrw_log_returns
+from .mrw import MRWGenerator, SMRWGenerator, mrw_log_returns, smrw_kernel, smrw_leverage, smrw_log_returns
 from .pdv import AutoregressiveLinearPredictor, PDVModel, PDVModelDiscrete
 from .pricing import PriceData, Smile, compute_smile
 from .statistics import realized_variance
@@ -22,6 +22,6 @@ __all__ = [
     "select_cartesian_product", "DiscreteProba", "Softmax", "Uniform", "realized_variance",
     "plot_closest", "plot_shadow", "plot_volatility", "PriceData", "Smile", "compute_smile",
     "PDVModel", "PDVModelDiscrete", "AutoregressiveLinearPredictor",
-    "MRWGenerator", "mrw_log_returns",
+    "MRWGenerator", "mrw_log_returns", "SMRWGenerator", "smrw_log_returns", "smrw_kernel", "smrw_leverage",
 ]
 __version__ = "0.1.0"

@@ -48,7 +48,7 @@ EXPORTS = ("psh_version", "psh_strerror", "psh_last_hip_error", "psh_workspace_b
            "psh_embedded_supported", "psh_embed_plan_offset", "psh_candidates_layout", "psh_workspace_init", "psh_last_comm_error", "psh_comm_unique_id", "psh_comm_create",
            "psh_comm_destroy", "psh_comm_world", "psh_exchange_merge", "psh_stream_create_reserving", "psh_stream_destroy",
            "psh_weighted_moments", "psh_realized_variance", "psh_count_nonfinite", "psh_smear_nonfinite", "psh_rows_nonfinite",
-           "psh_shadow_block_layout", "psh_shadow_blocking", "psh_hedged_mc", "psh_pdv_generate", "psh_mrw_generate")
+           "psh_shadow_block_layout", "psh_shadow_blocking", "psh_hedged_mc", "psh_pdv_generate", "psh_mrw_generate", "psh_smrw_generate")
 
 _lib = None
 
@@ -157,6 +157,9 @@ def load() -> C.CDLL:
                                                                                           vp, vp, vp, vp, vp]
     L.psh_mrw_generate.restype = i32
     L.psh_mrw_generate.argtypes = [i32, vp, i64, i32, C.c_double, vp, vp, C.c_double, C.c_uint64, vp, i64, vp, vp]
+    L.psh_smrw_generate.restype = i32
+    L.psh_smrw_generate.argtypes = [i32, vp, i64, i32, i32, C.c_double, vp, vp, C.c_double, C.c_double, C.c_uint64, vp, i64,
+                                    vp, vp]
     L.psh_gather_paths.restype = i32
     L.psh_gather_paths.argtypes = [i32, vp, vp, i64, i64, i64, i64, vp, i64, i32, vp]
     if L.psh_version() != PSH_VERSION:
@@ -1042,6 +1045,18 @@ MRW_OUTPUTS = ("dlnx", "lnx", "omega")
 PSH_MRW_MAX_N = 4096
 
 
+def _dlnx_rows(R: int, n: int, dev, dlnx_out):
+    """(tensor, row stride in floats) that takes R rows of n float32 returns: dlnx_out after its checks, or a fresh
+    (R, 1, n) tensor."""
+    if dlnx_out is None:
+        return torch.empty((R, 1, n), dtype=torch.float32, device=dev), n
+    if (not isinstance(dlnx_out, torch.Tensor) or dlnx_out.device != dev or dlnx_out.dtype != torch.float32 or
+            dlnx_out.dim() < 2 or dlnx_out.shape[0] != R or dlnx_out.shape[-1] < n or dlnx_out.stride(-1) != 1 or
+            (R > 1 and dlnx_out.stride(0) < n)):
+        raise ValueError(f"dlnx_out must be a float32 tensor on {dev} with {R} rows of >= {n} contiguous floats")
+    return dlnx_out, (dlnx_out.stride(0) if R > 1 else n)
+
+
 def mrw_generate(R: int, n: int, sigma: float, a_omega: torch.Tensor, a_eps: torch.Tensor | None, c0: float, *,
                  seed: int = 0, outputs=("dlnx",), dlnx_out: torch.Tensor | None = None) -> dict:
     """psh_mrw_generate: R multifractal random walks of n returns (shadowing_amd/mrw.py computes the tables).  a_omega,
@@ -1067,14 +1082,7 @@ def mrw_generate(R: int, n: int, sigma: float, a_omega: torch.Tensor, a_eps: tor
     out = {}
     stride = n
     if "dlnx" in outputs:
-        if dlnx_out is not None:
-            if (not isinstance(dlnx_out, torch.Tensor) or dlnx_out.device != dev or dlnx_out.dtype != torch.float32 or
-                    dlnx_out.dim() < 2 or dlnx_out.shape[0] != R or dlnx_out.shape[-1] < n or dlnx_out.stride(-1) != 1 or
-                    (R > 1 and dlnx_out.stride(0) < n)):
-                raise ValueError(f"dlnx_out must be a float32 tensor on {dev} with {R} rows of >= {n} contiguous floats")
-            out["dlnx"], stride = dlnx_out, (dlnx_out.stride(0) if R > 1 else n)
-        else:
-            out["dlnx"] = torch.empty((R, 1, n), dtype=torch.float32, device=dev)
+        out["dlnx"], stride = _dlnx_rows(R, n, dev, dlnx_out)
     if "lnx" in outputs:
         out["lnx"] = torch.empty((R, n + 1), dtype=torch.float64, device=dev)
     if "omega" in outputs:
@@ -1083,6 +1091,47 @@ def mrw_generate(R: int, n: int, sigma: float, a_omega: torch.Tensor, a_eps: tor
     _check(load().psh_mrw_generate(dev.index, _stream_ptr(dev), int(R), int(n), float(sigma), a_omega.data_ptr(),
                                    None if a_eps is None else a_eps.data_ptr(), float(c0), int(seed), ptr("dlnx"),
                                    int(stride), ptr("lnx"), ptr("omega")), "psh_mrw_generate")
+    return out
+
+
+SMRW_OUTPUTS = ("dlnx", "lnx", "logvol")
+
+
+def smrw_generate(R: int, n: int, m: int, sigma: float, a_omega: torch.Tensor, k_hat: torch.Tensor, c0: float, v: float, *,
+                  seed: int = 0, outputs=("dlnx",), dlnx_out: torch.Tensor | None = None) -> dict:
+    """psh_smrw_generate: R skewed multifractal random walks of n returns, m lags of leverage kernel
+    (shadowing_amd/mrw.py computes the tables).  a_omega: (M,) float64, k_hat: (M,) complex128 device tensors, M the
+    smallest power of two >= 2n, 1 <= m <= M - n.  Returns a dict of the requested `outputs` (of SMRW_OUTPUTS) as device
+    tensors: "dlnx" (R, 1, n) float32, "lnx" (R, n + 1) and "logvol" (R, n) float64.  dlnx_out: as mrw_generate.  Nothing
+    is synchronised."""
+    bad = [o for o in outputs if o not in SMRW_OUTPUTS]
+    if bad:
+        raise ValueError(f"unknown outputs {bad}; choose from {SMRW_OUTPUTS}")
+    if n > PSH_MRW_MAX_N:
+        raise ValueError(f"psh_smrw_generate makes paths of n <= {PSH_MRW_MAX_N} returns, got {n}")
+    M = 4
+    while M < 2 * n:
+        M *= 2
+    if not 1 <= m <= M - n:
+        raise ValueError(f"the memory must satisfy 1 <= m <= M - n = {M - n}, got {m}")
+    a_omega = _dev_tensor(a_omega, torch.float64, "a_omega")
+    dev = a_omega.device
+    k_hat = _dev_tensor(k_hat, torch.complex128, "k_hat")
+    for name, t in (("a_omega", a_omega), ("k_hat", k_hat)):
+        if tuple(t.shape) != (M,) or t.device != dev:
+            raise ValueError(f"{name} must hold M = {M} values on {dev}, got {tuple(t.shape)} on {t.device}")
+    out = {}
+    stride = n
+    if "dlnx" in outputs:
+        out["dlnx"], stride = _dlnx_rows(R, n, dev, dlnx_out)
+    if "lnx" in outputs:
+        out["lnx"] = torch.empty((R, n + 1), dtype=torch.float64, device=dev)
+    if "logvol" in outputs:
+        out["logvol"] = torch.empty((R, n), dtype=torch.float64, device=dev)
+    ptr = lambda name: out[name].data_ptr() if name in out else None   # noqa: E731
+    _check(load().psh_smrw_generate(dev.index, _stream_ptr(dev), int(R), int(n), int(m), float(sigma), a_omega.data_ptr(),
+                                    k_hat.data_ptr(), float(c0), float(v), int(seed), ptr("dlnx"), int(stride), ptr("lnx"),
+                                    ptr("logvol")), "psh_smrw_generate")
     return out
 
 

@@ -1520,4 +1520,25 @@ int psh_mrw_generate(int device, void* stream, int64_t R, int n, double sigma, c
     return PSH_OK;
 }
 
+int psh_smrw_generate(int device, void* stream, int64_t R, int n, int m, double sigma, const double* a_omega,
+                      const double* k_hat, double c0, double v, uint64_t seed, float* out_dlnx, int64_t dlnx_row_stride,
+                      double* out_lnx, double* out_logvol) {
+    if (!a_omega || !k_hat || R < 1 || n < 2 || m < 1 || !std::isfinite(sigma) || sigma < 0.0 || !std::isfinite(c0) ||
+        !std::isfinite(v) || (out_dlnx && dlnx_row_stride < n))
+        return PSH_ERR_ARG;
+    if (n > PSH_MRW_MAX_N || R >= ((int64_t)1 << 32)) return PSH_ERR_UNSUPPORTED;   // (the grid is R / 2 workgroups)
+    if (out_dlnx && R > INT64_MAX / dlnx_row_stride) return PSH_ERR_ARG;
+    SmrwArgs a{};
+    a.R = R; a.n = n; a.m = m; a.logM = 2;
+    while ((1 << a.logM) < 2 * n) ++a.logM;
+    if (m > (1 << a.logM) - n) return PSH_ERR_ARG;           // the convolution would wrap
+    a.sigma = sigma; a.cv = c0 + v; a.key0 = (uint32_t)seed; a.key1 = (uint32_t)(seed >> 32);
+    a.a_omega = a_omega; a.k_hat = (const double2*)k_hat;
+    a.dlnx = out_dlnx; a.dlnx_stride = dlnx_row_stride; a.lnx = out_lnx; a.logvol = out_logvol;
+    DeviceGuard g(device);
+    if (!g.ok) { snprintf(g_hip_err, sizeof(g_hip_err), "hipSetDevice(%d) failed", device); return PSH_ERR_HIP; }
+    HIP_TRY(launch_smrw(a, (hipStream_t)stream));
+    return PSH_OK;
+}
+
 }  // extern "C"

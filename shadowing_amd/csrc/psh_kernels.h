@@ -435,4 +435,19 @@ struct MrwArgs {
 };
 hipError_t launch_mrw(const MrwArgs& a, hipStream_t s);
 
+// psh_smrw.hip: the skewed multifractal random walk (psh_smrw_generate): white noise, lv = omega - A
+struct SmrwArgs {
+    int64_t R;                // paths; workgroup q makes paths 2q and 2q + 1
+    int n, m, logM;           // returns per path; lags of the leverage kernel, n + m <= M = 2^logM
+    double sigma, cv;         // r = sigma * eps * exp(lv - cv), cv = c0 + v
+    uint32_t key0, key1;      // the seed's low and high words
+    const double* a_omega;    // (M) as MrwArgs
+    const double2* k_hat;     // (M) conj(FFT_M(K))[k] exp(-2 pi i k m / M) / M: psh.h
+    float* dlnx;              // rows of n returns, dlnx_stride floats apart, or nullptr, as every output
+    int64_t dlnx_stride;
+    double* lnx;              // (R, n + 1)
+    double* logvol;           // (R, n)
+};
+hipError_t launch_smrw(const SmrwArgs& a, hipStream_t s);
+
 }  // namespace psh

@@ -1,5 +1,6 @@
-// psh_philox.h -- the counter-based generator psh_pdv.hip and psh_mrw.hip share: Random123's Philox4x32-10 keyed by the
-// 64-bit seed (key = (seed lo, seed hi)), the two 53-bit words of one call, and Box-Muller on them.  The numpy twin is
+// psh_philox.h -- the counter-based generator psh_pdv.hip, psh_mrw.hip and psh_smrw.hip share: Random123's
+// Philox4x32-10 keyed by the 64-bit seed (key = (seed lo, seed hi)), the two 53-bit words of one call, and Box-Muller on
+// them.  The numpy twin is
 // shadowing_amd/pdv.py (philox4x32_10, normal_pairs).
 //   counter (c0, c1, g lo, g hi) gives the 64-bit words a = (x1:x0) >> 11 and b = (x3:x2) >> 11;
 //   u1 = (a + 1) 2^-53 in (0, 1], u2 = b 2^-53 in [0, 1); rad = sqrt(-2 ln u1), z0 = rad cos(2 pi u2), z1 = rad sin(2 pi u2).
