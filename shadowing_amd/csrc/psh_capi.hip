@@ -38,6 +38,10 @@ struct DeviceGuard {   // launch on the caller's device, restore the previous on
     }
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
+// every entry point that launches: the rest of its body runs on `device`
+#define GUARD_DEVICE(device)                                                                 \
+    DeviceGuard g(device);                                                                   \
+    if (!g.ok) { snprintf(g_hip_err, sizeof(g_hip_err), "hipSetDevice(%d) failed", device); return PSH_ERR_HIP; }
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 inline int next_pow2(int x) { int p = 2; while (p < x) p <<= 1; return p; }
@@ -45,6 +49,23 @@ inline int tile_floats_for(int W) {
     const int logical = PSH_SEG + W + 32;               // SEG + W - 1 used, slack for the sliding refills
     return (logical + ((logical >> 6) << 2) + 8 + 3) & ~3;
 }
+// the matrix-core scans read the fp32 tile only window by window (no sliding refills past the segment): SEG + W - 1 values
+// rounded up to whole float4 stores, padded layout
+inline int mx_tile_floats(int W) {
+    const int logical = PSH_SEG + W + 3;
+    return (logical + ((logical >> 6) << 2) + 4 + 3) & ~3;
+}
+inline int64_t seg_count(int64_t Tp) { return (Tp + PSH_SEG - 1) / PSH_SEG; }     // wave-segments of PSH_SEG windows per row
+// a grid over `units` of work, `per_block` to a block: at most `resident` blocks (one round on the compute units), at most
+// `max_blocks` (the candidate slices: PSH_MAX_BLOCKS), at least one
+inline int64_t per_cu_grid(int64_t units, int per_block, int64_t resident, int64_t max_blocks = INT64_MAX) {
+    int64_t g = (units + per_block - 1) / per_block;
+    if (g > resident) g = resident;
+    if (g > max_blocks) g = max_blocks;
+    return g < 1 ? 1 : g;
+}
+// rows_kernel (one-window rows, a row per lane): 128 rows per block, up to eight blocks per compute unit
+inline int64_t rows_grid(int64_t n_rows, int ncu, int64_t max_blocks = INT64_MAX) { return per_cu_grid(n_rows, 128, 8 * (int64_t)ncu, max_blocks); }
 
 struct Workspace {
     FusedHdr* fused;      // state of the fused single-launch scan: ALWAYS the first PSH_FUSED_BYTES of the workspace
@@ -82,7 +103,7 @@ struct BootPlan { int64_t rows; int per_wave; int64_t entries; };
 // costs 2.2x a scan of the same rows: 0.58 of 4.9 ms at 512 queries with 1/16); the estimate's rank is then ~48.
 BootPlan boot_plan(int64_t R, int64_t Tp, int k, bool halves = false, bool estimate = false, bool thin = false, double margin = 12.0) {
     BootPlan bp{0, 0, 0};
-    const int64_t nseg = (Tp + PSH_SEG - 1) / PSH_SEG;
+    const int64_t nseg = seg_count(Tp);
     const int64_t quarter = R / 4;
     int64_t rows = estimate ? (thin ? R / 64 : R / 32) : R / 16;
     // >= 8k segment minima for the provable bound; an estimate wants its rank (~1.5 k x the sampled fraction + 16) well
@@ -170,7 +191,7 @@ static void stream_cand_list(const Workspace& w, int B, void** list, int* cap_pe
 // candidate capacity per query: the scan writes one slice per block (up to
 // PSH_MAX_BLOCKS of them), the exhaustive path one slot per window of a row chunk
 int recommended_cap(int64_t Tp, int k) {
-    const int64_t nseg = (Tp + PSH_SEG - 1) / PSH_SEG;
+    const int64_t nseg = seg_count(Tp);
     int64_t cap = 128 * (int64_t)PSH_MAX_BLOCKS;          // 128 entries per block slice
     if (cap < 64 * (int64_t)k) cap = 64 * (int64_t)k;
     if (cap < k + 4 * nseg * PSH_SEG) cap = k + 4 * nseg * PSH_SEG;   // exhaustive: >= 4 rows per chunk
@@ -220,6 +241,13 @@ int check_problem(const float* dataset, int64_t R, int64_t T, int64_t r_offset, 
     return PSH_OK;
 }
 
+// (row, t) packed into one 32-bit key -- rows r_offset .. r_offset + R - 1, t < Tp: the bits t takes, or -1 when the two do not fit
+inline int index_tbits(const Problem& p) {
+    int tb = 0;
+    while ((1ll << tb) < p.Tp) ++tb;
+    return ((p.R + p.r_offset) <= (1ll << (32 - tb))) ? tb : -1;
+}
+
 struct Plan { int grid; int n_qgroups; int q_per_group; int tile_floats; int wide; };
 #define PSH_RESERVED_CUS 4           // PSH_FLAG_RESERVE_CUS: compute units a scan leaves to the side stream (collective, merge)
 
@@ -249,54 +277,45 @@ inline Tuning tuning() {
 }
 inline int flags_of(const psh_profile* prof) { return prof ? prof->flags : 0; }
 
-int plan_scan(int device, const Problem& p, int64_t n_rows, Plan* plan) {
+// One scan call: where it runs, the caller's pointers, and what is read ONCE per call -- the flag word, the profile mode, the
+// device's CU count (behind the device guard), the tuning build's overrides.  Every route takes this, the Problem and the Workspace.
+struct Call {
+    int device; hipStream_t s;
+    const float* dataset; const float* queries; const float* qnorm;
+    float* out_d; int32_t* out_idx; int32_t* out_status;
+    psh_profile* profile;
+    int flags;            // psh_profile.flags (0 without a profile)
+    bool stages, events;  // PSH_PROFILE_STAGES; PSH_PROFILE_EVENTS with both events given
+    int ncu; Tuning tn;
+};
+Call make_call(int device, void* stream, const float* dataset, const float* queries, const float* qnorm,
+               float* out_d, int32_t* out_idx, int32_t* out_status, psh_profile* prof) {
+    return Call{device, (hipStream_t)stream, dataset, queries, qnorm, out_d, out_idx, out_status, prof, flags_of(prof),
+                prof && prof->mode == PSH_PROFILE_STAGES,
+                prof && prof->mode == PSH_PROFILE_EVENTS && prof->ev_scan_begin && prof->ev_scan_end, 0, tuning()};
+}
+
+int plan_scan(const Call& c, const Problem& p, int64_t n_rows, Plan* plan) {
     const int tile_floats = tile_floats_for(p.W);
-    // embedded scan of a batch: 512-thread blocks whose waves carry 12 (suffix rows: 6) queries per evaluation of the
-    // embedding (256 VGPRs, one block per CU)
-    const Tuning tn = tuning();
-    if (p.emx) {
-        // embed_mx_kernel: 8 waves (two per SIMD), one block per CU
-        int ncu = 0;
-        HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
-        const int nseg = (int)((p.Tp + PSH_SEG - 1) / PSH_SEG);
-        const int64_t n_rs = n_rows * nseg;
-        const int64_t waves = (int64_t)ncu * 8;
-        int n_qgroups = 1;
-        if (n_rs < waves && p.B > 1) {
-            int64_t g = (waves + n_rs - 1) / n_rs;
-            n_qgroups = (int)(g < p.B ? g : p.B);
-        }
-        const int q_per_group = (p.B + n_qgroups - 1) / n_qgroups;
-        n_qgroups = (p.B + q_per_group - 1) / q_per_group;
-        const int64_t units = n_rs * n_qgroups;
-        if (units >= (1ll << 31)) return PSH_ERR_UNSUPPORTED;
-        int64_t grid = (units + 7) / 8;
-        if (grid > ncu) grid = ncu;
-        if (grid > PSH_MAX_BLOCKS) grid = PSH_MAX_BLOCKS;
-        if (grid < 1) grid = 1;
-        plan->grid = (int)grid;
-        plan->n_qgroups = n_qgroups;
-        plan->q_per_group = q_per_group;
-        plan->tile_floats = tile_floats;
-        plan->wide = 0;
-        return PSH_OK;
+    int threads = 512, bpc = 1;       // embed_mx_kernel: 8 waves (two per SIMD), one block per CU
+    bool wide = false;
+    if (!p.emx) {
+        // embedded scan of a batch: 512-thread blocks whose waves carry 12 (suffix rows: 6) queries per evaluation of the
+        // embedding (256 VGPRs, one block per CU)
+        wide = p.ker && p.B >= c.tn.wide_min && !c.tn.narrow;
+        // a kernel matrix too large to sit in LDS beside sixteen wave tiles (Foveal(1.15, 0.9, 252): 39 x 252) runs the
+        // 8-wave instantiation whatever the batch size
+        if (p.ker && !wide && scan_shmem_bytes(tile_floats, p.B, p.emb_d, p.W, PSH_SCAN_THREADS) > PSH_LDS_BYTES) wide = true;
+        threads = wide ? 512 : PSH_SCAN_THREADS;
+        const size_t shmem = scan_shmem_bytes(tile_floats, p.B, p.emb_d, p.W, threads);
+        if (shmem > PSH_LDS_BYTES) return PSH_ERR_UNSUPPORTED;
+        if (!wide) HIP_TRY(scan_blocks_per_cu(p.W, p.aligned, p.ker != nullptr, shmem, &bpc));
+        if (c.tn.bpc > 0) bpc = c.tn.bpc;
+        if (bpc < 1) bpc = 1;
+        if (bpc > 8) bpc = 8;
     }
-    bool wide = p.ker && p.B >= tn.wide_min && !tn.narrow;
-    // a kernel matrix too large to sit in LDS beside sixteen wave tiles (Foveal(1.15, 0.9, 252): 39 x 252) runs the
-    // 8-wave instantiation whatever the batch size
-    if (p.ker && !wide && scan_shmem_bytes(tile_floats, p.B, p.emb_d, p.W, PSH_SCAN_THREADS) > PSH_LDS_BYTES) wide = true;
-    const int threads = wide ? 512 : PSH_SCAN_THREADS;
-    const size_t shmem = scan_shmem_bytes(tile_floats, p.B, p.emb_d, p.W, threads);
-    if (shmem > PSH_LDS_BYTES) return PSH_ERR_UNSUPPORTED;
-    int bpc = 1, ncu = 0;
-    if (!wide) HIP_TRY(scan_blocks_per_cu(p.W, p.aligned, p.ker != nullptr, shmem, &bpc));
-    HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
-    if (tn.bpc > 0) bpc = tn.bpc;
-    if (bpc < 1) bpc = 1;
-    if (bpc > 8) bpc = 8;
-    const int nseg = (int)((p.Tp + PSH_SEG - 1) / PSH_SEG);
-    const int64_t n_rs = n_rows * nseg;
-    const int64_t waves = (int64_t)bpc * ncu * (threads / 64);
+    const int64_t n_rs = n_rows * seg_count(p.Tp);
+    const int64_t waves = (int64_t)bpc * c.ncu * (threads / 64);
     // not enough (row, segment) units to fill the chip: also split the queries
     int n_qgroups = 1;
     if (n_rs < waves && p.B > 1) {
@@ -307,11 +326,7 @@ int plan_scan(int device, const Problem& p, int64_t n_rows, Plan* plan) {
     n_qgroups = (p.B + q_per_group - 1) / q_per_group;
     const int64_t units = n_rs * n_qgroups;
     if (units >= (1ll << 31)) return PSH_ERR_UNSUPPORTED;
-    int64_t grid = (units + (threads / 64) - 1) / (threads / 64);
-    if (grid > (int64_t)bpc * ncu) grid = (int64_t)bpc * ncu;
-    if (grid > PSH_MAX_BLOCKS) grid = PSH_MAX_BLOCKS;
-    if (grid < 1) grid = 1;
-    plan->grid = (int)grid;
+    plan->grid = (int)per_cu_grid(units, threads / 64, (int64_t)bpc * c.ncu, PSH_MAX_BLOCKS);
     plan->n_qgroups = n_qgroups;
     plan->q_per_group = q_per_group;
     plan->tile_floats = tile_floats;
@@ -319,14 +334,14 @@ int plan_scan(int device, const Problem& p, int64_t n_rows, Plan* plan) {
     return PSH_OK;
 }
 
-ScanArgs make_scan_args(const float* dataset, const float* queries, const Problem& p, const Workspace& w,
+ScanArgs make_scan_args(const Call& c, const Problem& p, const Workspace& w,
                         const Plan& plan, int64_t row0, int64_t row_stride, int64_t n_rows) {
     ScanArgs a;
     memset(&a, 0, sizeof(a));
-    a.dataset = dataset;
+    a.dataset = c.dataset;
     a.T = p.T;
     a.Tp = (int)p.Tp;
-    a.nseg = (int)((p.Tp + PSH_SEG - 1) / PSH_SEG);
+    a.nseg = (int)seg_count(p.Tp);
     a.W = p.W;
     a.row0 = row0;
     a.row_stride = row_stride;
@@ -337,16 +352,16 @@ ScanArgs make_scan_args(const float* dataset, const float* queries, const Proble
         a.magic_nseg = a.nseg > 1 ? (unsigned)((1ull << 32) / (uint64_t)a.nseg) : 0u;
     }
     a.r_offset = p.r_offset;
-    a.queries = queries;
+    a.queries = c.queries;
     a.ker = p.ker;
-    a.hx = p.ker ? queries : nullptr;
+    a.hx = p.ker ? c.queries : nullptr;
     a.emb_d = p.emb_d;
     a.emb_wide = plan.wide;
     a.emb_dense = p.emb_dense ? 1 : 0;                  // PSH_FLAG_EMBED_DENSE: skip the suffix-rows fast path (A/B tests)
     a.emb_mx = p.emx ? (p.emx_split ? 3 : 1) : 0;
     a.emb_taps = p.emb_taps ? 1 : 0;
-    a.emb_r1 = tuning().px_r1;
-    a.dbg = tuning().dbg;
+    a.emb_r1 = c.tn.px_r1;
+    a.dbg = c.tn.dbg;
     a.plan = p.eplan;
     a.B = p.B;
     a.n_qgroups = plan.n_qgroups;
@@ -364,10 +379,9 @@ ScanArgs make_scan_args(const float* dataset, const float* queries, const Proble
     return a;
 }
 
-// slices = true : rank what the FILTER scan left in `nblk` block slices
+// slices = true : rank what the FILTER scan left in `nblk` block slices; the queries' status words are written
 // slices = false: rank the first n_fixed flat entries (r < 0 = empty)
-SelectArgs make_select_args(const Problem& p, const Workspace& w, float* out_d, int32_t* out_idx, int* status,
-                            bool slices, int nblk, int n_fixed) {
+SelectArgs make_select_args(const Call& c, const Problem& p, const Workspace& w, bool slices, int nblk, int n_fixed) {
     SelectArgs s;
     memset(&s, 0, sizeof(s));
     s.cand_d = w.cand_d;
@@ -382,11 +396,11 @@ SelectArgs make_select_args(const Problem& p, const Workspace& w, float* out_d, 
     s.k = p.k;
     s.kpad = w.kpad;
     s.skip_negative_rows = slices ? 0 : 1;
-    s.out_d = out_d;
-    s.out_idx = out_idx;
+    s.out_d = c.out_d;
+    s.out_idx = c.out_idx;
     s.sel_rt = w.sel_rt;
     s.sort_scratch = reinterpret_cast<uint64_t*>(w.cand_rt);   // (r, t) of the selected are in sel_rt by the time the ordering runs
-    s.status = status;
+    s.status = slices ? c.out_status : nullptr;
     s.qstate = w.qstate;
     return s;
 }
@@ -428,55 +442,45 @@ struct Timer {   // optional per-stage HIP events
     ~Timer() { if (on) for (int i = 0; i < 8; ++i) (void)hipEventDestroy(ev[i]); }
 };
 
-int run_exhaustive(int device, hipStream_t s, const float* dataset, const float* queries, const float* qnorm,
-                   const Problem& p_in, const Workspace& w, float* out_d, int32_t* out_idx, int32_t* out_status,
-                   psh_profile* prof) {
+// ---- path 1: every window of the ensemble is ranked, a chunk of rows at a time
+int run_exhaustive(const Call& c, const Problem& p_in, const Workspace& w) {
     Problem p = p_in;
     p.emx = false;                 // every window is ranked here: the dense chains of embed_scan_kernel, no rejection test
     p.eplan = nullptr;
-    const int64_t nseg = (p.Tp + PSH_SEG - 1) / PSH_SEG;
+    psh_profile* const prof = c.profile;
     const bool rows_path = p.Tp == 1 && !p.ker && !p.rows_generic;   // one-window rows: a slot per row (rows_kernel)
-    const int64_t slots_per_row = rows_path ? 1 : nseg * PSH_SEG;
+    const int64_t slots_per_row = rows_path ? 1 : seg_count(p.Tp) * PSH_SEG;
     if ((int64_t)w.cap < (int64_t)p.k + slots_per_row) return PSH_ERR_WORKSPACE;
-    const bool stages = prof && prof->mode == PSH_PROFILE_STAGES;
-    const bool events = prof && prof->mode == PSH_PROFILE_EVENTS && prof->ev_scan_begin && prof->ev_scan_end;
-    Timer tm(stages, s);
+    Timer tm(c.stages, c.s);
     int rc = tm.init(); if (rc) return rc;
     rc = tm.mark(); if (rc) return rc;
-    PrepArgs pa{queries, qnorm, p.B, p.qlen, w.qstate, w.total, out_status};
-    HIP_TRY(launch_prep(pa, s));
+    PrepArgs pa{c.queries, c.qnorm, p.B, p.qlen, w.qstate, w.total, c.out_status};
+    HIP_TRY(launch_prep(pa, c.s));
     rc = tm.mark(); if (rc) return rc;
-    if (events) HIP_TRY(hipEventRecord((hipEvent_t)prof->ev_scan_begin, s));
+    if (c.events) HIP_TRY(hipEventRecord((hipEvent_t)prof->ev_scan_begin, c.s));
     int64_t rows_per_chunk = ((int64_t)w.cap - p.k) / slots_per_row;
     if (rows_per_chunk > p.R) rows_per_chunk = p.R;
     int grid_used = 0;
     for (int64_t r0 = 0; r0 < p.R; r0 += rows_per_chunk) {
         const int64_t nr = (r0 + rows_per_chunk <= p.R) ? rows_per_chunk : (p.R - r0);
         Plan plan;
-        rc = plan_scan(device, p, nr, &plan); if (rc) return rc;
+        rc = plan_scan(c, p, nr, &plan); if (rc) return rc;
         grid_used = plan.grid;
         const int n_slots = (int)(nr * slots_per_row);
         // the running best (empty on the first chunk) sits right behind the window slots
-        ReseedArgs ra{out_d, out_idx, w.qstate, w.cand_d, w.cand_rt, (int64_t)w.cap, n_slots, p.k};
-        HIP_TRY(launch_reseed(ra, p.B, s));
-        ScanArgs sa = make_scan_args(dataset, queries, p, w, plan, r0, 1, nr);
-        if (rows_path) {
-            int ncu = 0;
-            HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
-            int64_t gb = (nr + 127) / 128;
-            if (gb > 8 * (int64_t)ncu) gb = 8 * (int64_t)ncu;
-            HIP_TRY(launch_rows(sa, PSH_MODE_ALL, (int)(gb < 1 ? 1 : gb), s));
-        } else {
-            HIP_TRY(launch_scan(sa, PSH_MODE_ALL, p.aligned, plan.grid, s));
-        }
-        SelectArgs se = make_select_args(p, w, out_d, out_idx, nullptr, false, 0, n_slots + p.k);
-        HIP_TRY(launch_select(se, p.B, s));
+        ReseedArgs ra{c.out_d, c.out_idx, w.qstate, w.cand_d, w.cand_rt, (int64_t)w.cap, n_slots, p.k};
+        HIP_TRY(launch_reseed(ra, p.B, c.s));
+        ScanArgs sa = make_scan_args(c, p, w, plan, r0, 1, nr);
+        if (rows_path) HIP_TRY(launch_rows(sa, PSH_MODE_ALL, (int)rows_grid(nr, c.ncu), c.s));
+        else HIP_TRY(launch_scan(sa, PSH_MODE_ALL, p.aligned, plan.grid, c.s));
+        SelectArgs se = make_select_args(c, p, w, false, 0, n_slots + p.k);
+        HIP_TRY(launch_select(se, p.B, c.s));
     }
     rc = tm.mark(); if (rc) return rc;
-    if (events) HIP_TRY(hipEventRecord((hipEvent_t)prof->ev_scan_end, s));
+    if (c.events) HIP_TRY(hipEventRecord((hipEvent_t)prof->ev_scan_end, c.s));
     if (prof) { prof->path = 1; prof->grid_blocks = grid_used; prof->n_sample_rows = 0; }
-    if (stages) {
-        HIP_TRY(hipStreamSynchronize(s));
+    if (c.stages) {
+        HIP_TRY(hipStreamSynchronize(c.s));
         tm.elapsed(0, 1, &prof->prep_ms);
         tm.elapsed(1, 2, &prof->scan_ms);
         tm.elapsed(0, 2, &prof->total_ms);
@@ -518,8 +522,7 @@ int psh_workspace_bytes(int64_t R, int64_t T, int B, int W, int h, int k, size_t
 
 int psh_stream_create_reserving(int device, int reserve_cus, void** out_stream, int* out_reserved) {
     if (!out_stream || reserve_cus < 0) return PSH_ERR_ARG;
-    DeviceGuard g(device);
-    if (!g.ok) { snprintf(g_hip_err, sizeof(g_hip_err), "hipSetDevice(%d) failed", device); return PSH_ERR_HIP; }
+    GUARD_DEVICE(device);
     int ncu = 0;
     HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
     if (reserve_cus * 4 > ncu) reserve_cus = 0;             // a small device: nothing is reserved
@@ -545,8 +548,7 @@ int psh_stream_create_reserving(int device, int reserve_cus, void** out_stream, 
 
 int psh_stream_destroy(int device, void* stream) {
     if (!stream) return PSH_ERR_ARG;
-    DeviceGuard g(device);
-    if (!g.ok) { snprintf(g_hip_err, sizeof(g_hip_err), "hipSetDevice(%d) failed", device); return PSH_ERR_HIP; }
+    GUARD_DEVICE(device);
     HIP_TRY(hipStreamDestroy((hipStream_t)stream));
     return PSH_OK;
 }
@@ -554,44 +556,39 @@ int psh_stream_destroy(int device, void* stream) {
 int psh_workspace_init(int device, void* stream, void* workspace, size_t workspace_bytes) {
     if (!workspace || ((uintptr_t)workspace & 255u) != 0) return PSH_ERR_ARG;
     if (workspace_bytes < PSH_FUSED_BYTES) return PSH_ERR_WORKSPACE;
-    DeviceGuard g(device);
-    if (!g.ok) { snprintf(g_hip_err, sizeof(g_hip_err), "hipSetDevice(%d) failed", device); return PSH_ERR_HIP; }
+    GUARD_DEVICE(device);
     HIP_TRY(launch_fused_init((FusedHdr*)workspace, (hipStream_t)stream));
     return PSH_OK;
 }
 
 int psh_query_norm(int device, void* stream, const float* queries, int B, int W, float* out_qnorm) {
     if (!queries || !out_qnorm || B <= 0 || W <= 0) return PSH_ERR_ARG;
-    DeviceGuard g(device);
-    if (!g.ok) { snprintf(g_hip_err, sizeof(g_hip_err), "hipSetDevice(%d) failed", device); return PSH_ERR_HIP; }
+    GUARD_DEVICE(device);
     HIP_TRY(launch_qnorm(queries, B, W, out_qnorm, (hipStream_t)stream));
     return PSH_OK;
 }
 
-static int scan_exhaustive_impl(int device, void* stream, const float* dataset, int64_t R, int64_t T, int64_t r_offset,
-                                const float* queries, const float* qnorm, int B, int W, int h, int k,
-                                const float* ker, int emb_d,
-                                float* out_d, int32_t* out_idx, int32_t* out_status,
-                                void* workspace, size_t workspace_bytes, psh_profile* profile) {
+static int scan_exhaustive_impl(Call c, int64_t R, int64_t T, int64_t r_offset, int B, int W, int h, int k, const float* ker, int emb_d,
+                                void* workspace, size_t workspace_bytes) {
     Problem p;
-    int rc = check_problem(dataset, R, T, r_offset, queries, B, W, h, k, out_d, out_idx, &p, ker, emb_d);
+    int rc = check_problem(c.dataset, R, T, r_offset, c.queries, B, W, h, k, c.out_d, c.out_idx, &p, ker, emb_d);
     if (rc) return rc;
-    p.emb_dense = (flags_of(profile) & PSH_FLAG_EMBED_DENSE) != 0;
-    p.rows_generic = (flags_of(profile) & PSH_FLAG_ROWS_GENERIC) != 0;
+    p.emb_dense = (c.flags & PSH_FLAG_EMBED_DENSE) != 0;
+    p.rows_generic = (c.flags & PSH_FLAG_ROWS_GENERIC) != 0;
     Workspace w;
     rc = carve(workspace, workspace_bytes, B, k, boot_entries(p.R, p.Tp, k), &w);
     if (rc) return rc;
-    DeviceGuard g(device);
-    if (!g.ok) { snprintf(g_hip_err, sizeof(g_hip_err), "hipSetDevice(%d) failed", device); return PSH_ERR_HIP; }
-    return run_exhaustive(device, (hipStream_t)stream, dataset, queries, qnorm, p, w, out_d, out_idx, out_status, profile);
+    GUARD_DEVICE(c.device);
+    HIP_TRY(hipDeviceGetAttribute(&c.ncu, hipDeviceAttributeMultiprocessorCount, c.device));
+    return run_exhaustive(c, p, w);
 }
 
 int psh_scan_topk_exhaustive(int device, void* stream, const float* dataset, int64_t R, int64_t T, int64_t r_offset,
                              const float* queries, const float* qnorm, int B, int W, int h, int k,
                              float* out_d, int32_t* out_idx, int32_t* out_status,
                              void* workspace, size_t workspace_bytes, psh_profile* profile) {
-    return scan_exhaustive_impl(device, stream, dataset, R, T, r_offset, queries, qnorm, B, W, h, k, nullptr, 0,
-                                out_d, out_idx, out_status, workspace, workspace_bytes, profile);
+    return scan_exhaustive_impl(make_call(device, stream, dataset, queries, qnorm, out_d, out_idx, out_status, profile),
+                                R, T, r_offset, B, W, h, k, nullptr, 0, workspace, workspace_bytes);
 }
 
 int psh_scan_topk_embedded_exhaustive(int device, void* stream, const float* dataset, int64_t R, int64_t T,
@@ -601,8 +598,8 @@ int psh_scan_topk_embedded_exhaustive(int device, void* stream, const float* dat
                                       void* workspace, size_t workspace_bytes, psh_profile* profile) {
     if (!kernel || d <= 0) return PSH_ERR_ARG;
     if (T == (int64_t)K + h) return PSH_ERR_UNSUPPORTED;     // one-window rows: psh_embed_rows + psh_scan_topk (see psh.h)
-    return scan_exhaustive_impl(device, stream, dataset, R, T, r_offset, hx, hxnorm, B, K, h, k, kernel, d,
-                                out_d, out_idx, out_status, workspace, workspace_bytes, profile);
+    return scan_exhaustive_impl(make_call(device, stream, dataset, hx, hxnorm, out_d, out_idx, out_status, profile),
+                                R, T, r_offset, B, K, h, k, kernel, d, workspace, workspace_bytes);
 }
 
 // queries one step of the long-window scan serves (34 <= W <= 256): up to three -- as many as put their fragment tables in LDS beside
@@ -624,405 +621,353 @@ struct BlockingExtras {
     const float* q_host; const float* hint_host;      // the query (W floats) and, nullable, the admission level as the HOST reads them
 };
 
-static int scan_topk_impl(int device, void* stream, const float* dataset, int64_t R, int64_t T, int64_t r_offset,
-                          const float* queries, const float* qnorm, int B, int W, int h, int k,
-                          const float* ker, int emb_d,
-                          float* out_d, int32_t* out_idx, int32_t* out_status,
-                          void* workspace, size_t workspace_bytes, psh_profile* profile, BlockingExtras* bx = nullptr) {
-    Problem p;
-    int rc = check_problem(dataset, R, T, r_offset, queries, B, W, h, k, out_d, out_idx, &p, ker, emb_d);
-    if (rc) return rc;
-    if (!out_status) return PSH_ERR_ARG;
-    // Several queries with a window the batched kernels' bands do not reach (they stop at W = 25): a LOOP of the steps that do
-    // have a matrix-core rejection test, inside the call --
-    //   34 <= W <= 256: up to three queries per step (the three launches with the long-window scan, psh_stream.hip: the
-    //                   queries share the pass, the conversion and the energies' MFMAs);
-    //   26 <= W <= 33, four queries and more: three queries per step (the three launches' 2-3 query form).
-    // Round 6: what is left to the loop is PSH_FLAG_LONG_LOOP and shapes the batched long-window scan does not take (use_lq below
-    // serves four queries and more with 26 <= W <= 256 and two / three that do not ride one pass).
-    // The one-pass vector-ALU filter costs W fma per window and query: R = 32768, T = 4096, W = 126 -- 2 / 4 / 16 / 64 queries
-    // 1.14 / 2.19 / 8.6 / 33.6 ms in one pass, 0.34 / 0.65 / 2.6 / 10.6 ms as a loop; W = 252: 2.2 .. 67 against 0.50 .. 16.2 ms
-    // (tools/long_batch_probe.py).  Status words stay per query; a RETRY of any step sends the caller's WHOLE call to
-    // PSH_FLAG_NO_FUSE, as the protocol says.
-    const int long_q = long_queries_per_step(W);
-    // four queries and more with a long window -- or two / three that do not ride one pass of the three launches (W > 97 / 145:
-    // their tables do not fit beside the scan's rows) --: ONE pass per chunk of queries of the batched long-window scan (psh_lq.hip)
-    // through the separate launches' pipeline, instead of the loop of steps below
-    const bool use_lq = !ker && p.Tp > 1 && (B >= 4 || (long_q > 0 && B > long_q)) && scan_lq_supported(W, B, T) &&
-                        !(flags_of(profile) & (PSH_FLAG_FILTER_VALU | PSH_FLAG_NO_FUSE | PSH_FLAG_LONG_LOOP));
-    const int per_step = !ker && p.Tp > 1 ? (long_q > 0 && B > long_q ? long_q : (W >= 26 && W <= 33 && B > PSH_STREAM_MAX_Q ? PSH_STREAM_MAX_Q : 0)) : 0;
-    // (the loop pays only when its sub-calls get the three launches: 5 k candidates in a query's list of 65536, a sample of 256
-    //  units and more -- a call outside that would be B / 3 passes with the vector-ALU filter instead of one; psh_profile then
-    //  describes the LAST step of the loop: path, grid, and in PSH_PROFILE_EVENTS mode the bracket of that step's scan)
-    const bool step_fits = 5 * (int64_t)k <= 65536 && p.R * ((p.Tp + PSH_SEG - 1) / PSH_SEG) >= 1024;
-    if (per_step && step_fits && !use_lq && !(profile && profile->mode == PSH_PROFILE_STAGES) && !(flags_of(profile) & (PSH_FLAG_FILTER_VALU | PSH_FLAG_NO_FUSE))) {
-        psh_profile sub;
-        for (int b = 0; b < B; b += per_step) {
-            const int nb = B - b < per_step ? B - b : per_step;
-            if (profile) { sub = *profile; if (profile->tau_hint) sub.tau_hint = profile->tau_hint + b; }
-            rc = scan_topk_impl(device, stream, dataset, R, T, r_offset, queries + (size_t)b * W, qnorm ? qnorm + b : nullptr, nb, W, h, k,
-                                nullptr, 0, out_d + (size_t)b * k, out_idx + (size_t)b * k * 2, out_status + b, workspace, workspace_bytes,
-                                profile ? &sub : nullptr);
-            if (rc) return rc;
-        }
-        if (profile) { const float* hint0 = profile->tau_hint; *profile = sub; profile->tau_hint = hint0; }
-        return PSH_OK;
-    }
-    // A dense embedding's batch beyond what the matrix-core scan takes in one call (its per-query pass runs on the matrix cores
-    // for up to 256 queries -- PSH_EMX_QM_MAX_B -- and the queries' constants sit in LDS): chunks of the largest supported size inside the call instead of the vector-ALU
-    // scan for all of them (configs[4] with 512 query dates: 46 -> 10 ms per GPU).  Status words stay per query.
-    if (ker && (flags_of(profile) & PSH_FLAG_EMBED_MX) && !(flags_of(profile) & PSH_FLAG_EMBED_DENSE) && p.Tp > 1 && B > 3 &&
-        (B > 256 || !embed_mx_supported(emb_d, W, B, tile_floats_for(W))) && !(profile && profile->mode == PSH_PROFILE_STAGES)) {
-        int chunk = 0;
-        for (int c = B < 256 ? B : 256; c >= 3; c = c > 32 ? c - 32 : c - 1)
-            if (embed_mx_supported(emb_d, W, c, tile_floats_for(W))) { chunk = c; break; }
-        if (chunk >= 3) {
-            const int n_chunks = (B + chunk - 1) / chunk;
-            const int per = (B + n_chunks - 1) / n_chunks;                    // even chunks
-            psh_profile sub;
-            for (int b = 0; b < B; b += per) {
-                const int nb = B - b < per ? B - b : per;
-                if (profile) { sub = *profile; if (profile->tau_hint) sub.tau_hint = profile->tau_hint + b; }
-                rc = scan_topk_impl(device, stream, dataset, R, T, r_offset, queries + (size_t)b * emb_d, qnorm ? qnorm + b : nullptr, nb, W, h, k,
-                                    ker, emb_d, out_d + (size_t)b * k, out_idx + (size_t)b * k * 2, out_status + b, workspace, workspace_bytes,
-                                    profile ? &sub : nullptr);
-                if (rc) return rc;
-            }
-            if (profile) { const float* hint0 = profile->tau_hint; *profile = sub; profile->tau_hint = hint0; }
-            return PSH_OK;
-        }
-    }
-    p.emb_dense = (flags_of(profile) & PSH_FLAG_EMBED_DENSE) != 0;
-    p.rows_generic = (flags_of(profile) & PSH_FLAG_ROWS_GENERIC) != 0;
-    p.emb_taps = (flags_of(profile) & PSH_FLAG_EMBED_TAPS) != 0;
-    p.emx_split = (flags_of(profile) & PSH_FLAG_EMBED_MX_SPLIT) != 0;
-    p.emx = p.ker && (flags_of(profile) & PSH_FLAG_EMBED_MX) && !p.emb_dense && p.Tp > 1 &&
-            embed_mx_supported(p.emb_d, p.W, p.B, tile_floats_for(p.W));
-    Workspace w;
-    rc = carve(workspace, workspace_bytes, B, k, boot_entries(p.R, p.Tp, k), &w);
-    if (rc) return rc;
-    if ((int64_t)w.cap < (int64_t)k + ((p.Tp + PSH_SEG - 1) / PSH_SEG) * PSH_SEG) return PSH_ERR_WORKSPACE;
-    DeviceGuard g(device);
-    if (!g.ok) { snprintf(g_hip_err, sizeof(g_hip_err), "hipSetDevice(%d) failed", device); return PSH_ERR_HIP; }
-    hipStream_t s = (hipStream_t)stream;
-    // a linear embedding that may be Foveal-like on one interval: the matrix is looked at on the device (one small launch),
-    // and of the two kernels launched per stage the one the structure belongs to does the work (psh_embed_px.hip)
-    const bool want_plan = p.ker && !p.emb_dense && !p.emb_taps && !p.emx && p.Tp > 1 &&
-                           embed_px_supported(tile_floats_for(p.W), p.B, p.emb_d, p.W, false) &&
-                           embed_px_supported(tile_floats_for(p.W), p.B, p.emb_d, p.W, true);
-    // (in front of the decision between the sampled and the exhaustive path: with PSH_FLAG_EMBED_PLAN_KEEP the next call may
-    //  take the other one)
-    if (want_plan && !(flags_of(profile) & PSH_FLAG_EMBED_PLAN_KEEP)) HIP_TRY(launch_embed_plan(p.ker, p.emb_d, p.W, w.eplan, s));
+// Several queries with a window the batched kernels' bands do not reach (they stop at W = 25): who serves them.
+//   long_q:   queries one step of the three launches takes with this window (0: not a long window);
+//   use_lq:   four queries and more with a long window -- or two / three that do not ride one pass of the three launches (W > 97 /
+//             145: their tables do not fit beside the scan's rows) --: ONE pass per chunk of queries of the batched long-window scan
+//             (psh_lq.hip) through the separate launches' pipeline, instead of the loop of steps;
+//   per_step: a LOOP of the steps that do have a matrix-core rejection test, inside the call (scan_in_chunks) --
+//     34 <= W <= 256: up to three queries per step (the three launches with the long-window scan, psh_stream.hip: the
+//                     queries share the pass, the conversion and the energies' MFMAs);
+//     26 <= W <= 33, four queries and more: three queries per step (the three launches' 2-3 query form).
+// Round 6: what is left to the loop is PSH_FLAG_LONG_LOOP and shapes the batched long-window scan does not take (use_lq
+// serves four queries and more with 26 <= W <= 256 and two / three that do not ride one pass).
+// The one-pass vector-ALU filter costs W fma per window and query: R = 32768, T = 4096, W = 126 -- 2 / 4 / 16 / 64 queries
+// 1.14 / 2.19 / 8.6 / 33.6 ms in one pass, 0.34 / 0.65 / 2.6 / 10.6 ms as a loop; W = 252: 2.2 .. 67 against 0.50 .. 16.2 ms
+// (tools/long_batch_probe.py).
+struct LongPlan { int long_q; bool use_lq; int per_step; };
+static LongPlan plan_long(const Problem& p, int flags) {
+    LongPlan lp;
+    lp.long_q = long_queries_per_step(p.W);
+    lp.use_lq = !p.ker && p.Tp > 1 && (p.B >= 4 || (lp.long_q > 0 && p.B > lp.long_q)) && scan_lq_supported(p.W, p.B, p.T) &&
+                !(flags & (PSH_FLAG_FILTER_VALU | PSH_FLAG_NO_FUSE | PSH_FLAG_LONG_LOOP));
+    lp.per_step = !p.ker && p.Tp > 1 ? (lp.long_q > 0 && p.B > lp.long_q ? lp.long_q : (p.W >= 26 && p.W <= 33 && p.B > PSH_STREAM_MAX_Q ? PSH_STREAM_MAX_Q : 0)) : 0;
+    return lp;
+}
 
-    // small problems (everything fits the candidate buffer), one-window rows (their
-    // numerator uses another reduction order, handled by the exhaustive kernel only) or
-    // a sample too thin to be useful: exhaustive path
+static int scan_topk_impl(Call c, int64_t R, int64_t T, int64_t r_offset, int B, int W, int h, int k, const float* ker, int emb_d,
+                          void* workspace, size_t workspace_bytes, BlockingExtras* bx = nullptr);
+
+// The call as sub-calls of at most `per` queries each (the steps of a long window, the chunks of the matrix-core embedded
+// scan): outputs, status words, query norms and hints at the queries' offsets.  Status words stay per query; a RETRY of
+// any step sends the caller's WHOLE call to PSH_FLAG_NO_FUSE, as the protocol says.  psh_profile then describes the LAST
+// sub-call: path, grid, and in PSH_PROFILE_EVENTS mode the bracket of that step's scan (the caller's tau_hint pointer stays).
+static int scan_in_chunks(const Call& c, const Problem& p, int per, void* workspace, size_t workspace_bytes) {
+    psh_profile sub;
+    for (int b = 0; b < p.B; b += per) {
+        const int nb = p.B - b < per ? p.B - b : per;
+        Call cc = c;
+        cc.queries = c.queries + (size_t)b * p.qlen;
+        cc.qnorm = c.qnorm ? c.qnorm + b : nullptr;
+        cc.out_d = c.out_d + (size_t)b * p.k;
+        cc.out_idx = c.out_idx + (size_t)b * p.k * 2;
+        cc.out_status = c.out_status + b;
+        if (c.profile) { sub = *c.profile; if (sub.tau_hint) sub.tau_hint += b; cc.profile = &sub; }
+        const int rc = scan_topk_impl(cc, p.R, p.T, p.r_offset, nb, p.W, p.h, p.k, p.ker, p.emb_d, workspace, workspace_bytes);
+        if (rc) return rc;
+    }
+    if (c.profile) { const float* hint0 = c.profile->tau_hint; *c.profile = sub; c.profile->tau_hint = hint0; }
+    return PSH_OK;
+}
+
+// Which route serves a call, and the sample it draws: decided here, launched elsewhere.
+struct Route {
+    bool use_mx, use_mq, use_lq;        // the full scan's cheap test on the matrix cores: one query; batched (4 queries x 8 shifts per MFMA); batched, long window
+    bool mq_i8;                         // the batched scan's rejection test as the 8-bit product
+    bool rows_path, rows_wave_min;      // one-window rows (rows_kernel, a row per lane); their bootstrap keeps one minimum per chunk of 64 sampled rows
+    bool mx_estimate, boot_emx;         // one query with a large k admits below an estimate; the matrix-core embedded scan samples half segments itself
+    bool exhaustive;                    // path 1
+    int long_q;
+    BootPlan bp;
+    int64_t n_sample, stride, row0;     // the sampled rows: row0 + i * stride
+    const float* hint;                  // the caller's admission levels (psh_profile.tau_hint): no bootstrap sample anywhere
+};
+
+static Route decide_route(const Call& c, const Problem& p, const Workspace& w, const LongPlan& lp) {
+    Route rt{};
+    rt.long_q = lp.long_q;
+    rt.use_lq = lp.use_lq;
     // the cheap test of the full scan runs on the matrix cores where that is implemented
     // (PSH_FLAG_FILTER_VALU keeps it on the vector ALUs: comparison runs, tools/)
-    bool use_mx = !p.ker && scan_mx_supported(p.W, p.B);
-    bool use_mq = !p.ker && scan_mq_supported(p.W, p.B);      // batched queries: 4 queries x 8 shifts per MFMA
-    if (flags_of(profile) & PSH_FLAG_FILTER_VALU) use_mx = use_mq = false;
+    rt.use_mx = !p.ker && scan_mx_supported(p.W, p.B);
+    rt.use_mq = !p.ker && scan_mq_supported(p.W, p.B);
+    if (c.flags & PSH_FLAG_FILTER_VALU) rt.use_mx = rt.use_mq = false;
     // the batched scan's rejection test: the 8-bit product (scan_mq8_kernel) unless the caller asks for f16
     // (from 32 queries on: a segment's set-up is ~1.5 k cycles dearer with the 8-bit test -- two passes over the staged values, the
     //  energies turned into integers, the levels of every query -- and that is what a small batch pays for; 4 queries 230 against
     //  179 us per call, 16: 303 / 279, 32: 373 / 395, 128: 778 / 1083)
-    const bool mq_i8 = tuning().mq_i8 != 0 && !(flags_of(profile) & PSH_FLAG_MQ_F16) && (p.B >= 32 || tuning().mq_i8 > 1);
+    rt.mq_i8 = c.tn.mq_i8 != 0 && !(c.flags & PSH_FLAG_MQ_F16) && (p.B >= 32 || c.tn.mq_i8 > 1);
     // (half-segment mode measured for the single-query scan: bootstrap 17.4 -> 12.3 us, but tau admits twice as
     // much and the scan's exact rechecks cost 4.3 us more -- 135.7 vs 134.3 us per step; left off)
     // (the matrix-core embedded scan samples one minimum per HALF segment; a sample too thin for that plan is taken by
     // embed_scan_kernel instead -- the full scan still runs on the matrix cores)
-    BootPlan bp = boot_plan(p.R, p.Tp, k, p.emx, p.ker != nullptr || !use_mx, !p.ker && !use_mx);
+    rt.bp = boot_plan(p.R, p.Tp, p.k, p.emx, p.ker != nullptr || !rt.use_mx, !p.ker && !rt.use_mx);
     // A single query with a LARGE k (the reference's own example call: Identity(20), R = 32768, k = 8192 -- testing.ipynb): the
     // provable bound wants 8 k segment minima, more than a quarter of the rows have; the plan then fell to one minimum per LANE
     // (264 k minima, 0.19 ms to find the k-th among them, a bound that admitted 4.6 k candidates per k).  Such a call admits below
     // an ESTIMATE instead, like the embedded scans do: 1/32 of the rows, the r2-th smallest of their segment minima with ~1.5 k
     // windows of the ensemble expected below it; fewer than k found -> status -> the caller's exhaustive pass.
-    bool mx_estimate = false;
     // (a sample of moderate size keeps its provable bound: per lane up to 100 k minima, per segment up to an eighth of the rows)
-    if (use_mx && ((bp.per_wave == 0 && bp.entries > 100000) || (bp.per_wave == 1 && bp.rows * 8 > p.R))) {
-        const BootPlan be = boot_plan(p.R, p.Tp, k, false, true, false, 4.5);
-        if (be.per_wave == 1 && be.entries <= w.min_stride) { bp = be; mx_estimate = true; }
+    if (rt.use_mx && ((rt.bp.per_wave == 0 && rt.bp.entries > 100000) || (rt.bp.per_wave == 1 && rt.bp.rows * 8 > p.R))) {
+        const BootPlan be = boot_plan(p.R, p.Tp, p.k, false, true, false, 4.5);
+        if (be.per_wave == 1 && be.entries <= w.min_stride) { rt.bp = be; rt.mx_estimate = true; }
     }
-    const bool boot_emx = p.emx && bp.per_wave == 2;
-    if (p.emx && !boot_emx) bp = boot_plan(p.R, p.Tp, k, false, true);
+    rt.boot_emx = p.emx && rt.bp.per_wave == 2;
+    if (p.emx && !rt.boot_emx) rt.bp = boot_plan(p.R, p.Tp, p.k, false, true);
     // one-window rows (T == W + h; PathDistance.forward_topk's N pre-embedded points): rows_kernel, a row per lane.
     // Its bootstrap takes one exact value per sampled row.
-    const bool rows_path = p.Tp == 1 && !p.ker && !p.rows_generic;
-    bool rows_wave_min = false;
-    if (rows_path) {
-        const int frac = tuning().rows_frac;
-        int64_t ns = p.R / frac > 16 * (int64_t)k ? p.R / frac : 16 * (int64_t)k;
+    rt.rows_path = p.Tp == 1 && !p.ker && !p.rows_generic;
+    if (rt.rows_path) {
+        const int frac = c.tn.rows_frac;
+        int64_t ns = p.R / frac > 16 * (int64_t)p.k ? p.R / frac : 16 * (int64_t)p.k;
         if (ns > p.R / 2) ns = p.R / 2;
         if (ns > w.min_stride) ns = w.min_stride;
-        bp.rows = ns >= 2 * (int64_t)k ? ns : 0;
-        bp.per_wave = 1;
-        bp.entries = bp.rows;
-        // the estimate's rank (below) against the chunks of 64 rows of the sample: sparse enough -> one minimum per chunk
-        const int64_t r2r = (6 * (int64_t)k * bp.rows + 2 * p.R - 1) / (2 * p.R) + 16, chunks = (bp.rows + 63) / 64;
-        rows_wave_min = bp.rows > 0 && r2r < k && 8 * r2r <= chunks;
-        if (rows_wave_min) bp.entries = chunks;
-        use_mx = use_mq = false;
+        rt.bp.rows = ns >= 2 * (int64_t)p.k ? ns : 0;
+        rt.bp.per_wave = 1;
+        rt.bp.entries = rt.bp.rows;
+        // the estimate's rank (sample_ranks) against the chunks of 64 rows of the sample: sparse enough -> one minimum per chunk
+        const int64_t r2r = (6 * (int64_t)p.k * rt.bp.rows + 2 * p.R - 1) / (2 * p.R) + 16, chunks = (rt.bp.rows + 63) / 64;
+        rt.rows_wave_min = rt.bp.rows > 0 && r2r < p.k && 8 * r2r <= chunks;
+        if (rt.rows_wave_min) rt.bp.entries = chunks;
+        rt.use_mx = rt.use_mq = false;
     }
-    // the caller's admission levels (psh_profile.tau_hint): no bootstrap sample anywhere below
-    const float* hint = profile ? profile->tau_hint : nullptr;
-    const int64_t n_sample = bp.rows;
-    if (p.R * ((p.Tp + PSH_SEG - 1) / PSH_SEG) * PSH_SEG + k <= (int64_t)w.cap || (p.Tp == 1 && !rows_path) || (n_sample == 0 && !hint))
-        return run_exhaustive(device, s, dataset, queries, qnorm, p, w, out_d, out_idx, out_status, profile);
-    const int64_t stride = n_sample > 0 ? p.R / n_sample : 1;
-    const int64_t row0 = stride / 2;
-    if (want_plan) p.eplan = w.eplan;
+    rt.hint = c.profile ? c.profile->tau_hint : nullptr;
+    rt.n_sample = rt.bp.rows;
+    // small problems (everything fits the candidate buffer), one-window rows (their
+    // numerator uses another reduction order, handled by the exhaustive kernel only) or
+    // a sample too thin to be useful: exhaustive path
+    rt.exhaustive = p.R * seg_count(p.Tp) * PSH_SEG + p.k <= (int64_t)w.cap || (p.Tp == 1 && !rt.rows_path) || (rt.n_sample == 0 && !rt.hint);
+    rt.stride = rt.n_sample > 0 ? p.R / rt.n_sample : 1;
+    rt.row0 = rt.stride / 2;
+    return rt;
+}
 
-    const bool stages = profile && profile->mode == PSH_PROFILE_STAGES;
-    const bool events = profile && profile->mode == PSH_PROFILE_EVENTS && profile->ev_scan_begin && profile->ev_scan_end;
+// what the fused launch (path 2) and the three overlap-friendly launches (path 3) are told alike: a sample of `units` (row,
+// segment) units over `rows` rows spread over the ensemble, and the rank of the admission level among their minima
+static FusedArgs fused_args(const Call& c, const Problem& p, const Workspace& w, const Route& rt, int64_t units, int64_t rows, int64_t rank) {
+    FusedArgs fu;
+    memset(&fu, 0, sizeof(fu));
+    fu.hdr = w.fused;
+    fu.boot_units = (int)units;
+    fu.boot_row_stride = p.R / rows;
+    fu.boot_row0 = fu.boot_row_stride / 2;
+    fu.rank = (int)rank;
+    fu.qnorm_in = c.qnorm;
+    fu.out_d = c.out_d;
+    fu.out_idx = c.out_idx;
+    fu.status = c.out_status;
+    fu.total = w.total;
+    fu.tbits = index_tbits(p);
+    fu.tau_hint = rt.hint;
+    return fu;
+}
 
-    // ---- the step as three overlap-friendly launches (psh_stream.hip: sample + levels in one-wave blocks, the barrier-free
-    // scan, the ranking): ONE query when the caller says other steps are in flight on other streams (PSH_FLAG_OVERLAP), and
-    // always for two or three queries -- they ride one pass over the ensemble at about one query's cost, where the batched
-    // scan (sized for hundreds of queries) streams at half rate.
-    {
-        const bool small_batch = !p.ker && !rows_path && B >= 2 && B <= PSH_STREAM_MAX_Q && !(flags_of(profile) & PSH_FLAG_FILTER_VALU);
-        const bool one_overlap = use_mx && B == 1 && (flags_of(profile) & PSH_FLAG_OVERLAP);
-        // ONE query with a long window (34 <= W <= 256): the same three launches, flag or no flag, with the scan's banded product
-        // as a K-loop (stream_scan_long_kernel) -- otherwise such a call has only the vector-ALU filter of scan_kernel
-        // (the long-window scan's deferred survivors pack t into 30 bits)
-        const bool one_long = !p.ker && !rows_path && long_q > 0 && B <= long_q && !(flags_of(profile) & PSH_FLAG_FILTER_VALU) && p.T < (1ll << 30);
-        if ((small_batch || one_overlap || one_long) && !rows_path && !stages && !(flags_of(profile) & PSH_FLAG_NO_FUSE) &&
-            (scan_fused_supported(p.W) || one_long)) {
-            int ncu = 0;
-            HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
-            const Tuning tn = tuning();
-            const int64_t nseg = (p.Tp + PSH_SEG - 1) / PSH_SEG;
-            // a thinner sample than the fused launch's: its megabytes are HBM traffic beside ANOTHER step's scan here.  2048
-            // units (what the exchange area holds, split between the queries); the level is the r2p-th smallest minimum (below): the
-            // k best windows of the ensemble put kf = k x sampled fraction = 16 expected minima below their level at the benchmark's
-            // sizes, P(Poisson(16) >= 40) = 3e-7 that fewer than k windows lie below the estimate (-> PSH_STATUS_RETRY)
-            int64_t units_cap = tn.stream_units < 2048 ? tn.stream_units : 2048;     // (the sample kernel keeps a query's minima in registers: <= 2048)
-            // (a long window's exact sample chains cost W / 20 of the benchmark's: half the units -- the level's rank stays at its
-            //  floor of 24 with 8 minima expected below the k-th distance)
-            // (round 6: without a hint a long window's sample runs on the matrix cores -- stream_sample_long_kernel, upper bounds of the
-            //  minima -- and takes the full 2048 units; PSH_STREAM_SKIP bit 3 of the tuning build: the exact chains, for A/B runs)
-            const bool long_mx_sample = one_long && !hint && !(tn.stream_skip & 8) &&
-                                        stream_sample_long_shmem_bytes(p.W, B) <= (size_t)PSH_LDS_BYTES;
-            if (one_long && !long_mx_sample && units_cap > 1024) units_cap = 1024;
-            if (units_cap > PSH_FUSED_MAX_UNITS / B) units_cap = PSH_FUSED_MAX_UNITS / B;
-            int64_t rows_p = units_cap / nseg;
-            if (rows_p > p.R / 4) rows_p = p.R / 4;
-            if (rows_p < 1) rows_p = 1;
-            const int64_t units_p = rows_p * nseg;
-            // the level's rank among the sampled minima: the k best windows of the ensemble put at most kf = k x sampled fraction
-            // minima below their level (Poisson), so the (kf + 5 sqrt(kf) + 4)-th smallest lies above it but for five sigma -- 40 at
-            // the benchmark's kf = 16 (what 2 kf + 8 gave until round 6: the same there, but twelve sigma at kf = 128, where it
-            // admitted twice the windows a smooth ensemble's lists hold)
-            const double kf = (double)k * (double)rows_p / (double)p.R;
-            int64_t r2p = (int64_t)ceil(kf + 5.0 * sqrt(kf)) + 4;
-            if (r2p < 24) r2p = 24;
-            int64_t grid_p = (int64_t)tn.stream_pgrid_per_cu * ncu;
-            // (a long window's sample is its exact chains -- 1024 windows x W taps per unit, 11 us at W = 126 -- not its bytes:
-            //  one unit per wave instead of two, unless the caller says other steps' scans share the chip: three streams measured
-            //  +2 % with it, a lone stream's call 3 - 10 % less -- 3 queries with W = 126: 317 -> 284 us)
-            if (one_long && !(flags_of(profile) & PSH_FLAG_OVERLAP)) grid_p *= 2;
-            if (grid_p > units_p) grid_p = units_p;
-            int64_t grid_s = ncu;
-            // a stream made by psh_stream_create_reserving: one block per compute unit the stream may use
-            if ((flags_of(profile) & PSH_FLAG_RESERVE_CUS) && ncu >= 4 * PSH_STREAM_RESERVED_CUS) grid_s = ncu - PSH_STREAM_RESERVED_CUS;
-            const int64_t n_rs = p.R * nseg;
-            if (grid_s * (PSH_SCAN_THREADS / 64) > n_rs) grid_s = (n_rs + (PSH_SCAN_THREADS / 64) - 1) / (PSH_SCAN_THREADS / 64);
-            const int front = B == 1 ? PSH_FUSED_FRONT : 2 * PSH_FUSED_FRONT;
-            int cand_cap = 0;
-            void* cand_list = nullptr;
-            stream_cand_list(w, B, &cand_list, &cand_cap);
-            const int logical = PSH_SEG + p.W + 3;
-            const int tile_fl = (logical + ((logical >> 6) << 2) + 4 + 3) & ~3;
-            int tb = 0;
-            while ((1ll << tb) < p.Tp) ++tb;
-            if ((one_long ? stream_scan_long_shmem_bytes(p.W, B) : stream_scan_shmem_bytes_q(tile_fl, B)) <= PSH_LDS_BYTES &&
-                ((units_p >= 256 && r2p <= units_p / 2) || hint) &&
-                5 * (int64_t)k <= (int64_t)cand_cap && 5 * (int64_t)k * B <= grid_s * front * 2) {
-                Plan plan_s{(int)grid_s, 1, B, tile_fl, 0};
-                ScanArgs fa = make_scan_args(dataset, queries, p, w, plan_s, 0, 1, p.R);
-                fa.tile_floats = tile_fl;
-                fa.dbg_times = tn.dbg_times;
-                FusedArgs fu;
-                memset(&fu, 0, sizeof(fu));
-                fu.hdr = w.fused;
-                fu.boot_units = (int)units_p;
-                fu.boot_row_stride = p.R / rows_p;
-                fu.boot_row0 = fu.boot_row_stride / 2;
-                fu.rank = (int)r2p;
-                fu.qnorm_in = qnorm;
-                fu.out_d = out_d;
-                fu.out_idx = out_idx;
-                fu.status = out_status;
-                fu.total = w.total;
-                fu.tbits = ((p.R + p.r_offset) <= (1ll << (32 - tb))) ? tb : -1;   // rows r_offset .. r_offset + R - 1, t < Tp
-                fu.front = front;
-                fu.nq = B;
-                fu.units_stride = (int)((PSH_FUSED_MAX_UNITS / B) & ~3);
-                fu.cand_cap = cand_cap;
-                fu.cand_list = cand_list;
-                fu.k_out = k;
-                fu.tau_hint = hint;
-                if (hint) grid_p = 1;                  // nothing is sampled: one block derives scale, thresholds and the fragment table from the hints
-                if (!(tn.stream_skip & 1)) HIP_TRY(long_mx_sample ? launch_stream_sample_long(fa, fu, (int)grid_p, s)
-                                                                  : launch_stream_sample(fa, fu, p.aligned, (int)grid_p, tile_floats_for(p.W), s));
-                if (events) HIP_TRY(hipEventRecord((hipEvent_t)profile->ev_scan_begin, s));
-                if (!(tn.stream_skip & 4)) HIP_TRY(one_long ? launch_stream_scan_long(fa, fu, p.aligned, (int)grid_s, s)
-                                                            : launch_stream_scan(fa, fu, p.aligned, (int)grid_s, s));
-                if (events) HIP_TRY(hipEventRecord((hipEvent_t)profile->ev_scan_end, s));
-                // (~2.5 k candidates per query: <= 8 own ones per wave, ONE pass over all of them)
-                if (!(tn.stream_skip & 2)) HIP_TRY(launch_stream_rank(fa, fu, tn.stream_rgrid_per_cu * ncu, s));
-                if (profile) { profile->path = 3; profile->n_sample_rows = (int)rows_p; profile->grid_blocks = (int)grid_s; }
-                return PSH_OK;
-            }
-        }
+// ---- path 3: the step as three overlap-friendly launches (psh_stream.hip: sample + levels in one-wave blocks, the barrier-free
+// scan, the ranking): ONE query when the caller says other steps are in flight on other streams (PSH_FLAG_OVERLAP), and
+// always for two or three queries -- they ride one pass over the ensemble at about one query's cost, where the batched
+// scan (sized for hundreds of queries) streams at half rate.  *served: the launches are enqueued and the profile is filled.
+static int try_stream_step(const Call& c, const Problem& p, const Workspace& w, const Route& rt, bool* served) {
+    *served = false;
+    const int B = p.B;
+    const bool small_batch = !p.ker && !rt.rows_path && B >= 2 && B <= PSH_STREAM_MAX_Q && !(c.flags & PSH_FLAG_FILTER_VALU);
+    const bool one_overlap = rt.use_mx && B == 1 && (c.flags & PSH_FLAG_OVERLAP);
+    // ONE query with a long window (34 <= W <= 256): the same three launches, flag or no flag, with the scan's banded product
+    // as a K-loop (stream_scan_long_kernel) -- otherwise such a call has only the vector-ALU filter of scan_kernel
+    // (the long-window scan's deferred survivors pack t into 30 bits)
+    const bool one_long = !p.ker && !rt.rows_path && rt.long_q > 0 && B <= rt.long_q && !(c.flags & PSH_FLAG_FILTER_VALU) && p.T < (1ll << 30);
+    if (!((small_batch || one_overlap || one_long) && !rt.rows_path && !c.stages && !(c.flags & PSH_FLAG_NO_FUSE) &&
+          (scan_fused_supported(p.W) || one_long)))
+        return PSH_OK;
+    const Tuning& tn = c.tn;
+    const int64_t nseg = seg_count(p.Tp);
+    // a thinner sample than the fused launch's: its megabytes are HBM traffic beside ANOTHER step's scan here.  2048
+    // units (what the exchange area holds, split between the queries); the level is the r2p-th smallest minimum (below): the
+    // k best windows of the ensemble put kf = k x sampled fraction = 16 expected minima below their level at the benchmark's
+    // sizes, P(Poisson(16) >= 40) = 3e-7 that fewer than k windows lie below the estimate (-> PSH_STATUS_RETRY)
+    int64_t units_cap = tn.stream_units < 2048 ? tn.stream_units : 2048;     // (the sample kernel keeps a query's minima in registers: <= 2048)
+    // (a long window's exact sample chains cost W / 20 of the benchmark's: half the units -- the level's rank stays at its
+    //  floor of 24 with 8 minima expected below the k-th distance)
+    // (round 6: without a hint a long window's sample runs on the matrix cores -- stream_sample_long_kernel, upper bounds of the
+    //  minima -- and takes the full 2048 units; PSH_STREAM_SKIP bit 3 of the tuning build: the exact chains, for A/B runs)
+    const bool long_mx_sample = one_long && !rt.hint && !(tn.stream_skip & 8) &&
+                                stream_sample_long_shmem_bytes(p.W, B) <= (size_t)PSH_LDS_BYTES;
+    if (one_long && !long_mx_sample && units_cap > 1024) units_cap = 1024;
+    if (units_cap > PSH_FUSED_MAX_UNITS / B) units_cap = PSH_FUSED_MAX_UNITS / B;
+    int64_t rows_p = units_cap / nseg;
+    if (rows_p > p.R / 4) rows_p = p.R / 4;
+    if (rows_p < 1) rows_p = 1;
+    const int64_t units_p = rows_p * nseg;
+    // the level's rank among the sampled minima: the k best windows of the ensemble put at most kf = k x sampled fraction
+    // minima below their level (Poisson), so the (kf + 5 sqrt(kf) + 4)-th smallest lies above it but for five sigma -- 40 at
+    // the benchmark's kf = 16 (what 2 kf + 8 gave until round 6: the same there, but twelve sigma at kf = 128, where it
+    // admitted twice the windows a smooth ensemble's lists hold)
+    const double kf = (double)p.k * (double)rows_p / (double)p.R;
+    int64_t r2p = (int64_t)ceil(kf + 5.0 * sqrt(kf)) + 4;
+    if (r2p < 24) r2p = 24;
+    int64_t grid_p = (int64_t)tn.stream_pgrid_per_cu * c.ncu;
+    // (a long window's sample is its exact chains -- 1024 windows x W taps per unit, 11 us at W = 126 -- not its bytes:
+    //  one unit per wave instead of two, unless the caller says other steps' scans share the chip: three streams measured
+    //  +2 % with it, a lone stream's call 3 - 10 % less -- 3 queries with W = 126: 317 -> 284 us)
+    if (one_long && !(c.flags & PSH_FLAG_OVERLAP)) grid_p *= 2;
+    if (grid_p > units_p) grid_p = units_p;
+    int64_t grid_s = c.ncu;
+    // a stream made by psh_stream_create_reserving: one block per compute unit the stream may use
+    if ((c.flags & PSH_FLAG_RESERVE_CUS) && c.ncu >= 4 * PSH_STREAM_RESERVED_CUS) grid_s = c.ncu - PSH_STREAM_RESERVED_CUS;
+    const int64_t n_rs = p.R * nseg;
+    if (grid_s * (PSH_SCAN_THREADS / 64) > n_rs) grid_s = (n_rs + (PSH_SCAN_THREADS / 64) - 1) / (PSH_SCAN_THREADS / 64);
+    const int front = B == 1 ? PSH_FUSED_FRONT : 2 * PSH_FUSED_FRONT;
+    int cand_cap = 0;
+    void* cand_list = nullptr;
+    stream_cand_list(w, B, &cand_list, &cand_cap);
+    const int tile_fl = mx_tile_floats(p.W);
+    if (!((one_long ? stream_scan_long_shmem_bytes(p.W, B) : stream_scan_shmem_bytes_q(tile_fl, B)) <= PSH_LDS_BYTES &&
+          ((units_p >= 256 && r2p <= units_p / 2) || rt.hint) &&
+          5 * (int64_t)p.k <= (int64_t)cand_cap && 5 * (int64_t)p.k * B <= grid_s * front * 2))
+        return PSH_OK;
+    const Plan plan_s{(int)grid_s, 1, B, tile_fl, 0};
+    ScanArgs fa = make_scan_args(c, p, w, plan_s, 0, 1, p.R);
+    fa.dbg_times = tn.dbg_times;
+    FusedArgs fu = fused_args(c, p, w, rt, units_p, rows_p, r2p);
+    fu.front = front;
+    fu.nq = B;
+    fu.units_stride = (int)((PSH_FUSED_MAX_UNITS / B) & ~3);
+    fu.cand_cap = cand_cap;
+    fu.cand_list = cand_list;
+    fu.k_out = p.k;
+    if (rt.hint) grid_p = 1;                  // nothing is sampled: one block derives scale, thresholds and the fragment table from the hints
+    if (!(tn.stream_skip & 1)) HIP_TRY(long_mx_sample ? launch_stream_sample_long(fa, fu, (int)grid_p, c.s)
+                                                      : launch_stream_sample(fa, fu, p.aligned, (int)grid_p, tile_floats_for(p.W), c.s));
+    if (c.events) HIP_TRY(hipEventRecord((hipEvent_t)c.profile->ev_scan_begin, c.s));
+    if (!(tn.stream_skip & 4)) HIP_TRY(one_long ? launch_stream_scan_long(fa, fu, p.aligned, (int)grid_s, c.s)
+                                                : launch_stream_scan(fa, fu, p.aligned, (int)grid_s, c.s));
+    if (c.events) HIP_TRY(hipEventRecord((hipEvent_t)c.profile->ev_scan_end, c.s));
+    // (~2.5 k candidates per query: <= 8 own ones per wave, ONE pass over all of them)
+    if (!(tn.stream_skip & 2)) HIP_TRY(launch_stream_rank(fa, fu, tn.stream_rgrid_per_cu * c.ncu, c.s));
+    if (c.profile) { c.profile->path = 3; c.profile->n_sample_rows = (int)rows_p; c.profile->grid_blocks = (int)grid_s; }
+    *served = true;
+    return PSH_OK;
+}
+
+// ---- path 2: the whole step as ONE launch (psh_fused.hip): a single query on the matrix-core scan whose bootstrap sample is
+// one minimum per (row, segment) unit and fits the exchange area.  Anything that goes wrong inside raises
+// PSH_STATUS_RETRY in out_status and the caller reruns with PSH_FLAG_NO_FUSE.  `bx` (psh_shadow_blocking): the launch also
+// gathers the winners' paths and sets the completion words.  *served: the launch is enqueued and the profile is filled.
+static int try_fused_step(const Call& c, const Problem& p, const Workspace& w, const Route& rt, BlockingExtras* bx, bool* served) {
+    *served = false;
+    if (!(rt.use_mx && !rt.rows_path && !c.stages && !(c.flags & PSH_FLAG_NO_FUSE) && scan_fused_supported(p.W))) return PSH_OK;
+    Plan plan_f;
+    const int rc = plan_scan(c, p, p.R, &plan_f); if (rc) return rc;
+    if ((c.flags & PSH_FLAG_RESERVE_CUS) && plan_f.grid > 2 * PSH_RESERVED_CUS) plan_f.grid -= PSH_RESERVED_CUS;
+    // its own sample: only an ESTIMATE of the k-th smallest acc is needed (what is admitted is verified exactly, and
+    // "at least k admitted" proves the result complete), so at most PSH_FUSED_MAX_UNITS (row, segment) units -- one
+    // minimum each -- spread over at most a quarter of the ensemble
+    const int64_t nseg = seg_count(p.Tp);
+    int64_t rows_f = PSH_FUSED_MAX_UNITS / nseg;
+    if (rows_f > p.R / 4) rows_f = p.R / 4;
+    const int64_t units_f = rows_f * nseg;
+    // the admission level: the rank-th smallest sampled minimum -- ~2k windows of the whole ensemble expected below it
+    // (~3k when that rank is small and therefore noisy)
+    int64_t r2 = rows_f > 0 ? (2 * (int64_t)p.k * rows_f + p.R - 1) / p.R : 0;
+    r2 += r2 < 64 ? r2 / 2 + 16 : 8;
+    // (~2.5 k candidates are expected: they must fit the blocks' front lists with room to spare)
+    if (!(plan_f.grid <= PSH_FUSED_MAX_BLOCKS && ((rows_f >= 1 && units_f >= 256 && r2 <= units_f / 2) || rt.hint) &&
+          5 * (int64_t)p.k <= (int64_t)plan_f.grid * PSH_FUSED_FRONT))
+        return PSH_OK;
+    const int tile_fl = mx_tile_floats(p.W);
+    if (scan_fused_shmem_bytes(tile_fl) > PSH_LDS_BYTES) return PSH_OK;
+    // (a caller that asked for the overlap-friendly launches may be on a stream that cannot hold the fused
+    //  launch's blocks all at once -- a CU mask, other scans in flight: where they do not apply, the separate
+    //  launches serve the call, never the fused one)
+    if (c.flags & PSH_FLAG_OVERLAP) return PSH_OK;
+    ScanArgs fa = make_scan_args(c, p, w, plan_f, 0, 1, p.R);
+    fa.tile_floats = tile_fl;
+    fa.dbg_times = c.tn.dbg_times;
+    if (rows_f < 1) rows_f = 1;
+    FusedArgs fu = fused_args(c, p, w, rt, units_f, rows_f, r2);
+    // give-up time of a poll at the 100 MHz wall clock: 2 ms (a block that is not resident); 20 ms when a
+    // collective shares the chip (its workgroups may hold a few CUs until the peers arrive)
+    fu.spin_ticks = (c.flags & PSH_FLAG_RESERVE_CUS) ? 2000000 : 200000;
+    fu.xcd_skew = (plan_f.grid % 8 == 0) ? c.tn.xcd_skew : 0;      // (a grid that is not whole rounds of the 8 XCDs: no assumption)
+    if (bx) {
+        fu.g_ds = bx->g_ds; fu.g_out = bx->g_out; fu.g_T = bx->g_T; fu.g_C = bx->g_C; fu.g_len = bx->g_len;
+        fu.done = bx->done; fu.done_val = bx->done_val;
+        memcpy(fu.qv, bx->q_host, sizeof(float) * (size_t)p.W);              // (W <= 33: scan_fused_supported)
+        if (bx->hint_host) fu.hint_v = *bx->hint_host;
+        fu.done_shards = plan_f.grid < PSH_FUSED_DONE_SHARDS ? plan_f.grid : PSH_FUSED_DONE_SHARDS;
+        bx->taken = true; bx->shards = fu.done_shards;
     }
+    if (c.events) HIP_TRY(hipEventRecord((hipEvent_t)c.profile->ev_scan_begin, c.s));
+    HIP_TRY(launch_scan_fused(fa, fu, p.aligned, plan_f.grid, c.s));
+    if (c.events) HIP_TRY(hipEventRecord((hipEvent_t)c.profile->ev_scan_end, c.s));
+    if (c.profile) { c.profile->path = 2; c.profile->n_sample_rows = (int)rows_f; c.profile->grid_blocks = plan_f.grid; }
+    *served = true;
+    return PSH_OK;
+}
 
-    // ---- the whole step as ONE launch (psh_fused.hip): a single query on the matrix-core scan whose bootstrap sample is
-    // one minimum per (row, segment) unit and fits the exchange area.  Anything that goes wrong inside raises
-    // PSH_STATUS_RETRY in out_status and the caller reruns with PSH_FLAG_NO_FUSE.
-    if (use_mx && !rows_path && !stages && !(flags_of(profile) & PSH_FLAG_NO_FUSE) && scan_fused_supported(p.W)) {
-        Plan plan_f;
-        rc = plan_scan(device, p, p.R, &plan_f); if (rc) return rc;
-        if ((flags_of(profile) & PSH_FLAG_RESERVE_CUS) && plan_f.grid > 2 * PSH_RESERVED_CUS) plan_f.grid -= PSH_RESERVED_CUS;
-        // its own sample: only an ESTIMATE of the k-th smallest acc is needed (what is admitted is verified exactly, and
-        // "at least k admitted" proves the result complete), so at most PSH_FUSED_MAX_UNITS (row, segment) units -- one
-        // minimum each -- spread over at most a quarter of the ensemble
-        const int64_t nseg = (p.Tp + PSH_SEG - 1) / PSH_SEG;
-        int64_t rows_f = PSH_FUSED_MAX_UNITS / nseg;
-        if (rows_f > p.R / 4) rows_f = p.R / 4;
-        const int64_t units_f = rows_f * nseg;
-        // the admission level: the rank-th smallest sampled minimum -- ~2k windows of the whole ensemble expected below it
-        // (~3k when that rank is small and therefore noisy)
-        int64_t r2 = rows_f > 0 ? (2 * (int64_t)k * rows_f + p.R - 1) / p.R : 0;
-        r2 += r2 < 64 ? r2 / 2 + 16 : 8;
-        // (~2.5 k candidates are expected: they must fit the blocks' front lists with room to spare)
-        if (plan_f.grid <= PSH_FUSED_MAX_BLOCKS && ((rows_f >= 1 && units_f >= 256 && r2 <= units_f / 2) || hint) &&
-            5 * (int64_t)k <= (int64_t)plan_f.grid * PSH_FUSED_FRONT) {
-            if (rows_f < 1) rows_f = 1;
-            const int64_t stride_f = p.R / rows_f, row0_f = stride_f / 2;
-            ScanArgs fa = make_scan_args(dataset, queries, p, w, plan_f, 0, 1, p.R);
-            const int logical = PSH_SEG + p.W + 3;
-            fa.tile_floats = (logical + ((logical >> 6) << 2) + 4 + 3) & ~3;
-            if (scan_fused_shmem_bytes(fa.tile_floats) <= PSH_LDS_BYTES) {
-                FusedArgs fu;
-                memset(&fu, 0, sizeof(fu));
-                fu.hdr = w.fused;
-                fu.boot_units = (int)units_f;
-                fu.boot_row0 = row0_f;
-                fu.boot_row_stride = stride_f;
-                fu.rank = (int)r2;
-                fu.qnorm_in = qnorm;
-                fu.out_d = out_d;
-                fu.out_idx = out_idx;
-                fu.status = out_status;
-                fu.total = w.total;
-                fu.tau_hint = hint;
-                // give-up time of a poll at the 100 MHz wall clock: 2 ms (a block that is not resident); 20 ms when a
-                // collective shares the chip (its workgroups may hold a few CUs until the peers arrive)
-                fu.spin_ticks = (flags_of(profile) & PSH_FLAG_RESERVE_CUS) ? 2000000 : 200000;
-                {
-                    int tb = 0;
-                    while ((1ll << tb) < p.Tp) ++tb;
-                    fu.tbits = ((p.R + p.r_offset) <= (1ll << (32 - tb))) ? tb : -1;   // rows r_offset .. r_offset + R - 1, t < Tp
-                }
-                fu.xcd_skew = (plan_f.grid % 8 == 0) ? tuning().xcd_skew : 0;      // (a grid that is not whole rounds of the 8 XCDs: no assumption)
-                fa.dbg_times = tuning().dbg_times;
-                // (a caller that asked for the overlap-friendly launches may be on a stream that cannot hold the fused
-                //  launch's blocks all at once -- a CU mask, other scans in flight: where they do not apply, the separate
-                //  launches serve the call, never the fused one)
-                if (!(flags_of(profile) & PSH_FLAG_OVERLAP)) {
-                if (bx) {
-                    fu.g_ds = bx->g_ds; fu.g_out = bx->g_out; fu.g_T = bx->g_T; fu.g_C = bx->g_C; fu.g_len = bx->g_len;
-                    fu.done = bx->done; fu.done_val = bx->done_val;
-                    memcpy(fu.qv, bx->q_host, sizeof(float) * (size_t)p.W);              // (W <= 33: scan_fused_supported)
-                    if (bx->hint_host) fu.hint_v = *bx->hint_host;
-                    fu.done_shards = plan_f.grid < PSH_FUSED_DONE_SHARDS ? plan_f.grid : PSH_FUSED_DONE_SHARDS;
-                    bx->taken = true; bx->shards = fu.done_shards;
-                }
-                if (events) HIP_TRY(hipEventRecord((hipEvent_t)profile->ev_scan_begin, s));
-                HIP_TRY(launch_scan_fused(fa, fu, p.aligned, plan_f.grid, s));
-                if (events) HIP_TRY(hipEventRecord((hipEvent_t)profile->ev_scan_end, s));
-                if (profile) { profile->path = 2; profile->n_sample_rows = (int)rows_f; profile->grid_blocks = plan_f.grid; }
-                return PSH_OK;
-                }
-            }
-        }
-    }
-    Timer tm(stages, s);
-    rc = tm.init(); if (rc) return rc;
-    rc = tm.mark(); if (rc) return rc;                                       // 0
-    PrepArgs pa{queries, qnorm, B, p.qlen, w.qstate, w.total, out_status};  // runs inside the threshold kernel
-    rc = tm.mark(); if (rc) return rc;                                       // 1
-
+// ---- path 0, first launch: the bootstrap sample -- minima of the sampled rows into w.minbuf, for the threshold kernel.
+// *n_blockmax: the blocks whose max |y| the threshold kernel reads (the matrix-core scans' scale).
+static int launch_bootstrap(const Call& c, const Problem& p, const Workspace& w, const Route& rt, int* n_blockmax) {
+    const int64_t n_rows = rt.n_sample > 0 ? rt.n_sample : 1;
     Plan plan_s;
-    rc = plan_scan(device, p, n_sample > 0 ? n_sample : 1, &plan_s); if (rc) return rc;
-    ScanArgs sa = make_scan_args(dataset, queries, p, w, plan_s, row0, stride, n_sample > 0 ? n_sample : 1);
-    sa.boot_per_wave = bp.per_wave;
-    sa.emb_mx = boot_emx ? 1 : 0;
-    sa.blockmax = (use_mx || use_mq) ? w.blockmax : nullptr;
-    int n_blockmax = plan_s.grid;
+    const int rc = plan_scan(c, p, n_rows, &plan_s); if (rc) return rc;
+    ScanArgs sa = make_scan_args(c, p, w, plan_s, rt.row0, rt.stride, n_rows);
+    sa.boot_per_wave = rt.bp.per_wave;
+    sa.emb_mx = rt.boot_emx ? 1 : 0;
+    sa.blockmax = (rt.use_mx || rt.use_mq) ? w.blockmax : nullptr;
+    *n_blockmax = plan_s.grid;
     // the batch's tables and constants (the bootstrap's f16 copies, nx~, the f16 scale; the 8-bit test's step and residue
     // norms): whichever bootstrap follows, the threshold kernel reads the meta words
-    if (use_mq) HIP_TRY(launch_mq_prep(queries, B, p.W, w.mq_frag, s));
+    if (rt.use_mq) HIP_TRY(launch_mq_prep(c.queries, p.B, p.W, w.mq_frag, c.s));
     // (a single query is better served by the exact bootstrap: 8192 segments are a latency-bound launch either
     // way -- 20.8 vs 18.7 us measured -- and the exact minima admit 9 % fewer candidates)
-    if (hint) {
+    if (rt.hint) {
         // the caller's levels: nothing is sampled (the threshold kernel takes tau = tau2 = hint[b])
-        n_blockmax = 0;
-    } else if (use_mq && bp.per_wave == 1 && boot_mq_supported(p.W)) {
+        *n_blockmax = 0;
+    } else if (rt.use_mq && rt.bp.per_wave == 1 && boot_mq_supported(p.W)) {
         // segment minima as matrix-core upper bounds (boot_mq_kernel) instead of exact chains
-        int ncu = 0;
-        HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
-        const int chunks = boot_mq_chunks(B);
-        int64_t gx = (n_sample * sa.nseg + 7) / 8;
-        if (gx > ncu) gx = ncu;
+        const int chunks = boot_mq_chunks(p.B);
+        int64_t gx = per_cu_grid(rt.n_sample * sa.nseg, 8, c.ncu);
         while (gx * chunks > PSH_MAX_BLOCKS) gx /= 2;
         if (gx < 1) gx = 1;
-        n_blockmax = (int)gx * chunks;
+        *n_blockmax = (int)gx * chunks;
         sa.mq_frag = w.mq_frag;
-        {   // (the rank the threshold kernel will select, below: an estimate's rank -> the minima may be estimates too)
-            const int64_t r2e = (4 * (int64_t)k * n_sample + 2 * p.R - 1) / (2 * p.R) + 8;
-            sa.boot_estimate = (r2e < k && r2e <= bp.entries) ? 1 : 0;
-        }
-        HIP_TRY(launch_boot_mq(sa, p.aligned, (int)gx, s));
-    } else if (use_lq && bp.per_wave == 1) {
+        // (the rank the threshold kernel will select, sample_ranks: an estimate's rank -> the minima may be estimates too)
+        const int64_t r2e = (4 * (int64_t)p.k * rt.n_sample + 2 * p.R - 1) / (2 * p.R) + 8;
+        sa.boot_estimate = (r2e < p.k && r2e <= rt.bp.entries) ? 1 : 0;
+        HIP_TRY(launch_boot_mq(sa, p.aligned, (int)gx, c.s));
+    } else if (rt.use_lq && rt.bp.per_wave == 1) {
         // upper bounds of the segment minima of every query from the batched long-window kernel (one pass over the sampled rows)
-        int ncu = 0;
-        HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
-        sa.q_per_group = scan_lq_chunk(p.W, B);
-        sa.n_qgroups = (B + sa.q_per_group - 1) / sa.q_per_group;
-        int64_t gx = (n_sample * sa.nseg + 7) / 8;
-        if (gx > ncu) gx = ncu;
-        if (gx < 1) gx = 1;
-        HIP_TRY(launch_scan_lq(sa, PSH_MODE_BOOT, (int)gx, s));
-    } else if (rows_path) {
-        int ncu = 0;
-        HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
-        int64_t gb = (n_sample + 127) / 128;
-        if (gb > 8 * (int64_t)ncu) gb = 8 * (int64_t)ncu;
-        sa.boot_wave_min = rows_wave_min ? 1 : 0;
-        HIP_TRY(launch_rows(sa, PSH_MODE_BOOT, (int)(gb < 1 ? 1 : gb), s));
+        sa.q_per_group = scan_lq_chunk(p.W, p.B);
+        sa.n_qgroups = (p.B + sa.q_per_group - 1) / sa.q_per_group;
+        HIP_TRY(launch_scan_lq(sa, PSH_MODE_BOOT, (int)per_cu_grid(rt.n_sample * sa.nseg, 8, c.ncu), c.s));
+    } else if (rt.rows_path) {
+        sa.boot_wave_min = rt.rows_wave_min ? 1 : 0;
+        HIP_TRY(launch_rows(sa, PSH_MODE_BOOT, (int)rows_grid(rt.n_sample, c.ncu), c.s));
     } else {
-        HIP_TRY(launch_scan(sa, PSH_MODE_BOOT, p.aligned, plan_s.grid, s));
+        HIP_TRY(launch_scan(sa, PSH_MODE_BOOT, p.aligned, plan_s.grid, c.s));
     }
-    rc = tm.mark(); if (rc) return rc;                                       // 2
+    return PSH_OK;
+}
 
-    // single query on the matrix cores: candidates are filed in two classes around an ESTIMATE of the k-th
-    // smallest acc (the rank2-th smallest sampled minimum ~ 2k windows of the whole ensemble below it)
-    int rank2 = 0;
-    int k_thr = k;             // the rank the threshold kernel selects exactly
-    if (hint) {
+// path 0: the ranks the threshold kernel reads off the sample.  k_thr: the rank it selects exactly (the admission level);
+// rank2 > 0: a single query on the matrix cores files its candidates in two classes around an ESTIMATE of the k-th
+// smallest acc (the rank2-th smallest sampled minimum ~ 2k windows of the whole ensemble below it).
+struct SampleRanks { int k_thr; int rank2; };
+static SampleRanks sample_ranks(const Problem& p, const Route& rt) {
+    SampleRanks sr{p.k, 0};
+    const int64_t k = p.k, n_sample = rt.n_sample;
+    if (rt.hint) {
         // one class of candidates below the caller's level
-    } else if (use_mx && mx_estimate) {
+    } else if (rt.use_mx && rt.mx_estimate) {
         // the number of sampled minima below the ensemble's k-th smallest value is ~ Binomial(entries, k / windows): mean m = k x
         // the sampled fraction, deviation sqrt(m) -- the rank m + 4.5 sqrt(m) + 8 falls short of k windows once in ~10^5 calls
         // (-> status -> the exhaustive pass) and admits ~1.3 k candidates at k = 8192 instead of the 1.6 k of a flat 1.5 m
         const double m = (double)k * (double)n_sample / (double)p.R;
         const int64_t r2 = (int64_t)(m + 4.5 * sqrt(m) + 8.0) + 1;
-        if (r2 < k && r2 <= bp.entries) k_thr = (int)r2;
-    } else if (use_mx) {
-        const int64_t r2 = (2 * (int64_t)k * n_sample + p.R - 1) / p.R + 8;
-        rank2 = (r2 < k && r2 <= bp.entries) ? (int)r2 : 0;
+        if (r2 < k && r2 <= rt.bp.entries) sr.k_thr = (int)r2;
+    } else if (rt.use_mx) {
+        const int64_t r2 = (2 * k * n_sample + p.R - 1) / p.R + 8;
+        sr.rank2 = (r2 < k && r2 <= rt.bp.entries) ? (int)r2 : 0;
     } else {            // every other scan: the embedded ones, one-window rows, the batched matrix-core scan, the VALU-filter scans
         // The embedded scan (and the scan of one-window rows) ADMITS below an estimate: a candidate costs it an exact
         // d x K chain, and the provable tau of a 1/16 sample lets ~16 k of them through.  The estimate is the r2-th
@@ -1038,118 +983,177 @@ static int scan_topk_impl(int device, void* stream, const float* dataset, int64_
         // (the thin 1/64 sample of the batched / VALU-filter scans: + 8 on a rank of ~32 -- k windows of the ensemble
         //  put 16 expected minima of the sample below their level, P(Poisson(16) >= 40) = 3e-7 per query; the minima are
         //  upper bounds, which only adds to the margin)
-        const bool thin = !p.ker && !rows_path;
-        const int64_t r2 = ((p.ker ? 3 : (rows_path ? 6 : 4)) * (int64_t)k * n_sample + 2 * p.R - 1) / (2 * p.R) + (thin ? 8 : 16);
-        if (r2 < k && r2 <= bp.entries) k_thr = (int)r2;
+        const bool thin = !p.ker && !rt.rows_path;
+        const int64_t r2 = ((p.ker ? 3 : (rt.rows_path ? 6 : 4)) * k * n_sample + 2 * p.R - 1) / (2 * p.R) + (thin ? 8 : 16);
+        if (r2 < k && r2 <= rt.bp.entries) sr.k_thr = (int)r2;
     }
-    ThresholdArgs ta{w.minbuf, w.min_stride, hint ? 0 : (int)bp.entries, w.qstate, k_thr, 0,
-                     ((use_mx || use_mq) && !hint) ? w.blockmax : nullptr, n_blockmax, use_mq ? w.mq_frag : nullptr, mq_i8 ? 1 : 0, rank2, pa, hint};
-    HIP_TRY(launch_threshold(ta, B, s));
-    rc = tm.mark(); if (rc) return rc;                                       // 3
+    return sr;
+}
 
+// ---- path 0, third launch: the full scan, admitting below the threshold kernel's levels into one slice of the candidate
+// arrays per block.  *nblk: the blocks whose slices the selection reads.
+static int launch_filter(const Call& c, const Problem& p, const Workspace& w, const Route& rt, int rank2, int* nblk) {
     Plan plan_f;
-    rc = plan_scan(device, p, p.R, &plan_f); if (rc) return rc;
+    const int rc = plan_scan(c, p, p.R, &plan_f); if (rc) return rc;
     // a CU-masked stream (psh_stream_create_reserving): one resident round of blocks on the compute units it may use
-    if ((flags_of(profile) & PSH_FLAG_RESERVE_CUS) && (flags_of(profile) & PSH_FLAG_OVERLAP) && plan_f.grid > 4 * PSH_STREAM_RESERVED_CUS && !p.ker)
+    if ((c.flags & PSH_FLAG_RESERVE_CUS) && (c.flags & PSH_FLAG_OVERLAP) && plan_f.grid > 4 * PSH_STREAM_RESERVED_CUS && !p.ker)
         plan_f.grid -= PSH_STREAM_RESERVED_CUS;
-    ScanArgs fa = make_scan_args(dataset, queries, p, w, plan_f, 0, 1, p.R);
-    fa.use_mx = use_mx ? 1 : 0;
-    fa.bcount2 = (use_mx && rank2 > 0) ? w.bcount2 : nullptr;
-    if (use_mx) {
-        // scan_mx_kernel reads the fp32 tile only window by window (no sliding refills past the segment):
-        // SEG + W - 1 values rounded up to whole float4 stores, padded layout -- every byte counts, the
-        // kernel uses 155+ of the 160 KB of LDS
-        const int logical = PSH_SEG + p.W + 3;
-        fa.tile_floats = (logical + ((logical >> 6) << 2) + 4 + 3) & ~3;
-    }
-    fa.dbg_times = tuning().dbg_times;
-    if (events) HIP_TRY(hipEventRecord((hipEvent_t)profile->ev_scan_begin, s));
-    int nblk = plan_f.grid;
-    if (use_mq) {
+    ScanArgs fa = make_scan_args(c, p, w, plan_f, 0, 1, p.R);
+    fa.use_mx = rt.use_mx ? 1 : 0;
+    fa.bcount2 = (rt.use_mx && rank2 > 0) ? w.bcount2 : nullptr;
+    // scan_mx_kernel reads the fp32 tile only window by window (no sliding refills past the segment):
+    // SEG + W - 1 values rounded up to whole float4 stores, padded layout -- every byte counts, the
+    // kernel uses 155+ of the 160 KB of LDS
+    if (rt.use_mx) fa.tile_floats = mx_tile_floats(p.W);
+    fa.dbg_times = c.tn.dbg_times;
+    if (c.events) HIP_TRY(hipEventRecord((hipEvent_t)c.profile->ev_scan_begin, c.s));
+    *nblk = plan_f.grid;
+    if (rt.use_mq || rt.use_lq) {
         // one block of 8 waves per CU and query chunk (grid.y); a query's candidates come from the blocks of its
         // chunk only, so slices are indexed by blockIdx.x alone.  (A 16x16x32 layout -- 2 queries x 8 shifts per
         // MFMA, 12 waves per block at 168 VGPRs -- was built and measured: 6.4 ms against 4.7 for the scan.)
-        int ncu = 0;
-        HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
-        const int chunks = scan_mq_chunks(B);
-        const int64_t n_rs = p.R * ((p.Tp + PSH_SEG - 1) / PSH_SEG);
-        int64_t gx = (n_rs + 7) / 8;
-        if (gx > ncu) gx = ncu;
-        if (gx > PSH_MAX_BLOCKS) gx = PSH_MAX_BLOCKS;
-        if (gx < 1) gx = 1;
-        (void)chunks;
-        nblk = (int)gx;
-        fa.mq_frag = w.mq_frag;
-        fa.mq_i8 = mq_i8 ? 1 : 0;
-        fa.slice = w.cap / nblk;
-        HIP_TRY(launch_scan_mq(fa, p.aligned, (int)gx, s));
-    } else if (use_lq) {
-        int ncu = 0;
-        HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
-        fa.q_per_group = scan_lq_chunk(p.W, B);
-        fa.n_qgroups = (B + fa.q_per_group - 1) / fa.q_per_group;
-        const int64_t n_rs = p.R * ((p.Tp + PSH_SEG - 1) / PSH_SEG);
-        int64_t gx = (n_rs + 7) / 8;
-        if (gx > ncu) gx = ncu;
-        if (gx > PSH_MAX_BLOCKS) gx = PSH_MAX_BLOCKS;
-        if (gx < 1) gx = 1;
-        nblk = (int)gx;
-        fa.slice = w.cap / nblk;
-        HIP_TRY(launch_scan_lq(fa, PSH_MODE_FILTER, nblk, s));
-    } else if (rows_path) {
-        int ncu = 0;
-        HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
-        int64_t gb = (p.R + 127) / 128;
-        if (gb > 8 * (int64_t)ncu) gb = 8 * (int64_t)ncu;
-        if (gb > PSH_MAX_BLOCKS) gb = PSH_MAX_BLOCKS;
-        nblk = (int)(gb < 1 ? 1 : gb);
-        fa.slice = w.cap / nblk;
-        HIP_TRY(launch_rows(fa, PSH_MODE_FILTER, nblk, s));
+        *nblk = (int)per_cu_grid(p.R * seg_count(p.Tp), 8, c.ncu, PSH_MAX_BLOCKS);
+        fa.slice = w.cap / *nblk;
+        if (rt.use_mq) {
+            fa.mq_frag = w.mq_frag;
+            fa.mq_i8 = rt.mq_i8 ? 1 : 0;
+            HIP_TRY(launch_scan_mq(fa, p.aligned, *nblk, c.s));
+        } else {
+            fa.q_per_group = scan_lq_chunk(p.W, p.B);
+            fa.n_qgroups = (p.B + fa.q_per_group - 1) / fa.q_per_group;
+            HIP_TRY(launch_scan_lq(fa, PSH_MODE_FILTER, *nblk, c.s));
+        }
+    } else if (rt.rows_path) {
+        *nblk = (int)rows_grid(p.R, c.ncu, PSH_MAX_BLOCKS);
+        fa.slice = w.cap / *nblk;
+        HIP_TRY(launch_rows(fa, PSH_MODE_FILTER, *nblk, c.s));
     } else {
-        HIP_TRY(launch_scan(fa, PSH_MODE_FILTER, p.aligned, plan_f.grid, s));
+        HIP_TRY(launch_scan(fa, PSH_MODE_FILTER, p.aligned, plan_f.grid, c.s));
     }
-    if (events) HIP_TRY(hipEventRecord((hipEvent_t)profile->ev_scan_end, s));
-    rc = tm.mark(); if (rc) return rc;                                       // 4
+    if (c.events) HIP_TRY(hipEventRecord((hipEvent_t)c.profile->ev_scan_end, c.s));
+    return PSH_OK;
+}
 
-    SelectArgs se = make_select_args(p, w, out_d, out_idx, out_status, true, nblk, 0);
-    se.unsorted_ok = (flags_of(profile) & PSH_FLAG_UNSORTED) ? 1 : 0;
-    se.bcount2 = (use_mx && rank2 > 0) ? w.bcount2 : nullptr;
-    if (use_mx && rank2 > 0) { se.dataset = dataset; se.queries = queries; se.T = p.T; se.r_offset = p.r_offset; se.W = p.W; }
-    se.dbg_times = tuning().dbg_select;
+// ---- path 0, last launch: the k best of what the scan left in its `nblk` block slices
+static int launch_selection(const Call& c, const Problem& p, const Workspace& w, const Route& rt, int rank2, int nblk) {
+    SelectArgs se = make_select_args(c, p, w, true, nblk, 0);
+    se.unsorted_ok = (c.flags & PSH_FLAG_UNSORTED) ? 1 : 0;
+    se.bcount2 = (rt.use_mx && rank2 > 0) ? w.bcount2 : nullptr;
+    if (rt.use_mx && rank2 > 0) { se.dataset = c.dataset; se.queries = c.queries; se.T = p.T; se.r_offset = p.r_offset; se.W = p.W; }
+    se.dbg_times = c.tn.dbg_select;
     // (the flags sit behind the B <= 8 totals in their 256-byte slot of the workspace: ints 32 .. 39)
-    if (B <= PSH_RANK_MAX_B && !(flags_of(profile) & PSH_FLAG_SELECT_ONE_BLOCK)) {
-        int tb = 0;
-        while ((1ll << tb) < p.Tp) ++tb;
-        se.rank_tbits = ((p.R + p.r_offset) <= (1ll << (32 - tb))) ? tb : -1;   // rows r_offset .. r_offset + R - 1, t < Tp
+    if (p.B <= PSH_RANK_MAX_B && !(c.flags & PSH_FLAG_SELECT_ONE_BLOCK)) {
+        se.rank_tbits = index_tbits(p);
         se.handled = w.total + 32;
     }
-    HIP_TRY(launch_select(se, B, s));
-    rc = tm.mark(); if (rc) return rc;                                       // 5
+    HIP_TRY(launch_select(se, p.B, c.s));
+    return PSH_OK;
+}
 
+// ---- path 0: the separate launches -- bootstrap sample, threshold, filter scan, selection
+static int run_sampled(const Call& c, const Problem& p, const Workspace& w, const Route& rt) {
+    psh_profile* const profile = c.profile;
+    Timer tm(c.stages, c.s);
+    int rc = tm.init(); if (rc) return rc;
+    rc = tm.mark(); if (rc) return rc;                                       // 0
+    PrepArgs pa{c.queries, c.qnorm, p.B, p.qlen, w.qstate, w.total, c.out_status};  // runs inside the threshold kernel
+    rc = tm.mark(); if (rc) return rc;                                       // 1
+    int n_blockmax = 0;
+    rc = launch_bootstrap(c, p, w, rt, &n_blockmax); if (rc) return rc;
+    rc = tm.mark(); if (rc) return rc;                                       // 2
+    const SampleRanks sr = sample_ranks(p, rt);
+    ThresholdArgs ta{w.minbuf, w.min_stride, rt.hint ? 0 : (int)rt.bp.entries, w.qstate, sr.k_thr, 0,
+                     ((rt.use_mx || rt.use_mq) && !rt.hint) ? w.blockmax : nullptr, n_blockmax, rt.use_mq ? w.mq_frag : nullptr,
+                     rt.mq_i8 ? 1 : 0, sr.rank2, pa, rt.hint};
+    HIP_TRY(launch_threshold(ta, p.B, c.s));
+    rc = tm.mark(); if (rc) return rc;                                       // 3
+    int nblk = 0;
+    rc = launch_filter(c, p, w, rt, sr.rank2, &nblk); if (rc) return rc;
+    rc = tm.mark(); if (rc) return rc;                                       // 4
+    rc = launch_selection(c, p, w, rt, sr.rank2, nblk); if (rc) return rc;
+    rc = tm.mark(); if (rc) return rc;                                       // 5
     if (profile) {
         profile->path = 0;
-        profile->n_sample_rows = hint ? 0 : (int)n_sample;
+        profile->n_sample_rows = rt.hint ? 0 : (int)rt.n_sample;
         profile->grid_blocks = nblk;           // the blocks whose slices the selection read (psh_candidates_layout)
     }
-    if (stages) {
-        HIP_TRY(hipStreamSynchronize(s));
+    if (c.stages) {
+        HIP_TRY(hipStreamSynchronize(c.s));
         tm.elapsed(0, 1, &profile->prep_ms);
         tm.elapsed(1, 2, &profile->sample_ms);
         tm.elapsed(2, 3, &profile->threshold_ms);
         tm.elapsed(3, 4, &profile->scan_ms);
         tm.elapsed(4, 5, &profile->select_ms);
         tm.elapsed(0, 5, &profile->total_ms);
-        rc = max_total(w, B, &profile->n_candidates); if (rc) return rc;
+        rc = max_total(w, p.B, &profile->n_candidates); if (rc) return rc;
     }
     return PSH_OK;
+}
+
+// psh_scan_topk, psh_scan_topk_embedded (ker, emb_d) and psh_shadow_blocking (bx): check, the chunk loops, then
+// carve -> device guard -> embed plan -> route -> exhaustive? the three launches? the fused launch? the separate launches
+static int scan_topk_impl(Call c, int64_t R, int64_t T, int64_t r_offset, int B, int W, int h, int k, const float* ker, int emb_d,
+                          void* workspace, size_t workspace_bytes, BlockingExtras* bx) {
+    Problem p;
+    int rc = check_problem(c.dataset, R, T, r_offset, c.queries, B, W, h, k, c.out_d, c.out_idx, &p, ker, emb_d);
+    if (rc) return rc;
+    if (!c.out_status) return PSH_ERR_ARG;
+    const LongPlan lp = plan_long(p, c.flags);
+    // (the loop pays only when its sub-calls get the three launches: 5 k candidates in a query's list of 65536, a sample of 256
+    //  units and more -- a call outside that would be B / 3 passes with the vector-ALU filter instead of one)
+    const bool step_fits = 5 * (int64_t)k <= 65536 && p.R * seg_count(p.Tp) >= 1024;
+    if (lp.per_step && step_fits && !lp.use_lq && !c.stages && !(c.flags & (PSH_FLAG_FILTER_VALU | PSH_FLAG_NO_FUSE)))
+        return scan_in_chunks(c, p, lp.per_step, workspace, workspace_bytes);
+    // A dense embedding's batch beyond what the matrix-core scan takes in one call (its per-query pass runs on the matrix cores
+    // for up to 256 queries -- PSH_EMX_QM_MAX_B -- and the queries' constants sit in LDS): chunks of the largest supported size inside the call instead of the vector-ALU
+    // scan for all of them (configs[4] with 512 query dates: 46 -> 10 ms per GPU).  Status words stay per query.
+    if (p.ker && (c.flags & PSH_FLAG_EMBED_MX) && !(c.flags & PSH_FLAG_EMBED_DENSE) && p.Tp > 1 && B > 3 &&
+        (B > 256 || !embed_mx_supported(emb_d, W, B, tile_floats_for(W))) && !c.stages) {
+        int chunk = 0;
+        for (int n = B < 256 ? B : 256; n >= 3; n = n > 32 ? n - 32 : n - 1)
+            if (embed_mx_supported(emb_d, W, n, tile_floats_for(W))) { chunk = n; break; }
+        if (chunk >= 3) {
+            const int n_chunks = (B + chunk - 1) / chunk;
+            return scan_in_chunks(c, p, (B + n_chunks - 1) / n_chunks, workspace, workspace_bytes);   // even chunks
+        }
+    }
+    p.emb_dense = (c.flags & PSH_FLAG_EMBED_DENSE) != 0;
+    p.rows_generic = (c.flags & PSH_FLAG_ROWS_GENERIC) != 0;
+    p.emb_taps = (c.flags & PSH_FLAG_EMBED_TAPS) != 0;
+    p.emx_split = (c.flags & PSH_FLAG_EMBED_MX_SPLIT) != 0;
+    p.emx = p.ker && (c.flags & PSH_FLAG_EMBED_MX) && !p.emb_dense && p.Tp > 1 &&
+            embed_mx_supported(p.emb_d, p.W, p.B, tile_floats_for(p.W));
+    Workspace w;
+    rc = carve(workspace, workspace_bytes, B, k, boot_entries(p.R, p.Tp, k), &w);
+    if (rc) return rc;
+    if ((int64_t)w.cap < (int64_t)k + seg_count(p.Tp) * PSH_SEG) return PSH_ERR_WORKSPACE;
+    GUARD_DEVICE(c.device);
+    HIP_TRY(hipDeviceGetAttribute(&c.ncu, hipDeviceAttributeMultiprocessorCount, c.device));
+    // a linear embedding that may be Foveal-like on one interval: the matrix is looked at on the device (one small launch),
+    // and of the two kernels launched per stage the one the structure belongs to does the work (psh_embed_px.hip)
+    const bool want_plan = p.ker && !p.emb_dense && !p.emb_taps && !p.emx && p.Tp > 1 &&
+                           embed_px_supported(tile_floats_for(p.W), p.B, p.emb_d, p.W, false) &&
+                           embed_px_supported(tile_floats_for(p.W), p.B, p.emb_d, p.W, true);
+    // (in front of the decision between the sampled and the exhaustive path: with PSH_FLAG_EMBED_PLAN_KEEP the next call may
+    //  take the other one)
+    if (want_plan && !(c.flags & PSH_FLAG_EMBED_PLAN_KEEP)) HIP_TRY(launch_embed_plan(p.ker, p.emb_d, p.W, w.eplan, c.s));
+    const Route rt = decide_route(c, p, w, lp);
+    if (rt.exhaustive) return run_exhaustive(c, p, w);
+    if (want_plan) p.eplan = w.eplan;
+    bool served = false;
+    rc = try_stream_step(c, p, w, rt, &served);
+    if (rc || served) return rc;
+    rc = try_fused_step(c, p, w, rt, bx, &served);
+    if (rc || served) return rc;
+    return run_sampled(c, p, w, rt);
 }
 
 int psh_scan_topk(int device, void* stream, const float* dataset, int64_t R, int64_t T, int64_t r_offset,
                   const float* queries, const float* qnorm, int B, int W, int h, int k,
                   float* out_d, int32_t* out_idx, int32_t* out_status,
                   void* workspace, size_t workspace_bytes, psh_profile* profile) {
-    return scan_topk_impl(device, stream, dataset, R, T, r_offset, queries, qnorm, B, W, h, k, nullptr, 0,
-                          out_d, out_idx, out_status, workspace, workspace_bytes, profile);
+    return scan_topk_impl(make_call(device, stream, dataset, queries, qnorm, out_d, out_idx, out_status, profile),
+                          R, T, r_offset, B, W, h, k, nullptr, 0, workspace, workspace_bytes);
 }
 
 int psh_scan_topk_embedded(int device, void* stream, const float* dataset, int64_t R, int64_t T, int64_t r_offset,
@@ -1158,8 +1162,8 @@ int psh_scan_topk_embedded(int device, void* stream, const float* dataset, int64
                            void* workspace, size_t workspace_bytes, psh_profile* profile) {
     if (!kernel || d <= 0) return PSH_ERR_ARG;
     if (T == (int64_t)K + h) return PSH_ERR_UNSUPPORTED;     // one-window rows: psh_embed_rows + psh_scan_topk (see psh.h)
-    return scan_topk_impl(device, stream, dataset, R, T, r_offset, hx, hxnorm, B, K, h, k, kernel, d,
-                          out_d, out_idx, out_status, workspace, workspace_bytes, profile);
+    return scan_topk_impl(make_call(device, stream, dataset, hx, hxnorm, out_d, out_idx, out_status, profile),
+                          R, T, r_offset, B, K, h, k, kernel, d, workspace, workspace_bytes);
 }
 
 int psh_merge_workspace_bytes(int B, int k, size_t* out_bytes) {
@@ -1176,8 +1180,7 @@ int psh_merge_topk(int device, void* stream, const float* d_lists, const int32_t
     if (((uintptr_t)idx_lists & 7u) != 0 || ((uintptr_t)workspace & 7u) != 0) return PSH_ERR_ARG;
     const int kpad = next_pow2(k);
     if (workspace_bytes < sizeof(int2) * (size_t)B * kpad) return PSH_ERR_WORKSPACE;
-    DeviceGuard g(device);
-    if (!g.ok) { snprintf(g_hip_err, sizeof(g_hip_err), "hipSetDevice(%d) failed", device); return PSH_ERR_HIP; }
+    GUARD_DEVICE(device);
     SelectArgs s;
     memset(&s, 0, sizeof(s));
     s.cand_d = d_lists;
@@ -1207,8 +1210,7 @@ int psh_merge_topk_gathered(int device, void* stream, const float* d_gathered, c
     if (((uintptr_t)idx_gathered & 7u) != 0 || ((uintptr_t)workspace & 7u) != 0) return PSH_ERR_ARG;
     const int kpad = next_pow2(k);
     if (workspace_bytes < sizeof(int2) * (size_t)B * kpad) return PSH_ERR_WORKSPACE;
-    DeviceGuard g(device);
-    if (!g.ok) { snprintf(g_hip_err, sizeof(g_hip_err), "hipSetDevice(%d) failed", device); return PSH_ERR_HIP; }
+    GUARD_DEVICE(device);
     SelectArgs s;
     memset(&s, 0, sizeof(s));
     s.cand_d = d_gathered;
@@ -1237,8 +1239,7 @@ int psh_merge_sorted_gathered(int device, void* stream, const float* d_gathered,
     if (rank_stride < (int64_t)B * k_in || rank_stride_idx < (int64_t)B * k_in) return PSH_ERR_ARG;
     if (((uintptr_t)idx_gathered & 7u) != 0) return PSH_ERR_ARG;
     if (G > 64 || (int64_t)G * k_in * 4 > 128 * 1024 || (int64_t)k > (int64_t)G * k_in + PSH_MAX_K) return PSH_ERR_UNSUPPORTED;
-    DeviceGuard g(device);
-    if (!g.ok) { snprintf(g_hip_err, sizeof(g_hip_err), "hipSetDevice(%d) failed", device); return PSH_ERR_HIP; }
+    GUARD_DEVICE(device);
     MergeSortedArgs m{d_gathered, (const int2*)idx_gathered, rank_stride, rank_stride_idx, G, k_in, k, out_d, out_idx};
     HIP_TRY(launch_merge_sorted(m, B, (hipStream_t)stream));
     return PSH_OK;
@@ -1287,8 +1288,7 @@ int psh_embed_rows(int device, void* stream, const float* dataset, int64_t R, in
                    const float* kernel, int d, int K, float* out) {
     if (!dataset || !kernel || !out || R <= 0 || T <= 0 || d <= 0 || K <= 0 || K > T) return PSH_ERR_ARG;
     if (d > PSH_EMB_MAX_D || (int64_t)d * ((K + 3) & ~3) > PSH_EMB_MAX_TAPS) return PSH_ERR_UNSUPPORTED;
-    DeviceGuard g(device);
-    if (!g.ok) { snprintf(g_hip_err, sizeof(g_hip_err), "hipSetDevice(%d) failed", device); return PSH_ERR_HIP; }
+    GUARD_DEVICE(device);
     HIP_TRY(launch_embed_rows(dataset, R, T, kernel, d, K, out, (hipStream_t)stream));
     return PSH_OK;
 }
@@ -1296,8 +1296,7 @@ int psh_embed_rows(int device, void* stream, const float* dataset, int64_t R, in
 int psh_gather_paths(int device, void* stream, const float* dataset, int64_t R, int64_t C, int64_t T, int64_t r_offset,
                      const int32_t* idx, int64_t n, int len, float* out) {
     if (!dataset || !idx || !out || R <= 0 || C <= 0 || T <= 0 || n < 0 || len <= 0) return PSH_ERR_ARG;
-    DeviceGuard g(device);
-    if (!g.ok) { snprintf(g_hip_err, sizeof(g_hip_err), "hipSetDevice(%d) failed", device); return PSH_ERR_HIP; }
+    GUARD_DEVICE(device);
     GatherArgs a{dataset, R, C, T, r_offset, idx, n, (int64_t)len, out};
     HIP_TRY(launch_gather(a, (hipStream_t)stream));
     return PSH_OK;
@@ -1345,14 +1344,13 @@ int psh_shadow_blocking(int device, void* stream, const float* rows, int64_t R, 
                       const_cast<unsigned*>(done), seq, false, 0,
                       reinterpret_cast<const float*>(hb + PSH_SHADOW_OFF_QUERY), with_hint ? reinterpret_cast<const float*>(hb + PSH_SHADOW_OFF_HINT) : nullptr};
     __atomic_thread_fence(__ATOMIC_SEQ_CST);                                   // query, hint, status: in memory before the doorbell
-    rc = scan_topk_impl(device, stream, rows, R, T, r_offset, reinterpret_cast<const float*>(hb + PSH_SHADOW_OFF_QUERY), nullptr,
-                        1, W, h, k, nullptr, 0, reinterpret_cast<float*>(hb + lay[4]), reinterpret_cast<int32_t*>(hb + lay[5]), status,
-                        workspace, workspace_bytes, &pf, &bx);
+    rc = scan_topk_impl(make_call(device, stream, rows, reinterpret_cast<const float*>(hb + PSH_SHADOW_OFF_QUERY), nullptr,
+                                  reinterpret_cast<float*>(hb + lay[4]), reinterpret_cast<int32_t*>(hb + lay[5]), status, &pf),
+                        R, T, r_offset, 1, W, h, k, nullptr, 0, workspace, workspace_bytes, &bx);
     if (profile) { const float* th = profile->tau_hint; const int md = profile->mode; void* e0 = profile->ev_scan_begin; void* e1 = profile->ev_scan_end;
                    *profile = pf; profile->tau_hint = th; profile->mode = md; profile->ev_scan_begin = e0; profile->ev_scan_end = e1; }
     if (rc) return rc;
-    DeviceGuard g(device);
-    if (!g.ok) { snprintf(g_hip_err, sizeof(g_hip_err), "hipSetDevice(%d) failed", device); return PSH_ERR_HIP; }
+    GUARD_DEVICE(device);
     hipStream_t s = (hipStream_t)stream;
     if (!bx.taken) {
         // not the fused launch (a window or a k it does not serve, a small ensemble): the gather as its own launch, and the
@@ -1394,16 +1392,14 @@ int psh_shadow_blocking(int device, void* stream, const float* rows, int64_t R, 
 
 int psh_count_nonfinite(int device, void* stream, const float* x, int64_t n, unsigned long long* out_count) {
     if (!x || !out_count || n < 0) return PSH_ERR_ARG;
-    DeviceGuard g(device);
-    if (!g.ok) { snprintf(g_hip_err, sizeof(g_hip_err), "hipSetDevice(%d) failed", device); return PSH_ERR_HIP; }
+    GUARD_DEVICE(device);
     HIP_TRY(launch_count_nonfinite(x, n, out_count, (hipStream_t)stream));
     return PSH_OK;
 }
 
 int psh_rows_nonfinite(int device, void* stream, const float* dataset, int64_t R, int64_t C, int64_t T, int32_t* out_flags) {
     if (!dataset || !out_flags || R < 0 || C <= 0 || T <= 0) return PSH_ERR_ARG;
-    DeviceGuard g(device);
-    if (!g.ok) { snprintf(g_hip_err, sizeof(g_hip_err), "hipSetDevice(%d) failed", device); return PSH_ERR_HIP; }
+    GUARD_DEVICE(device);
     HIP_TRY(launch_rows_nonfinite(dataset, R, C * T, out_flags, (hipStream_t)stream));
     return PSH_OK;
 }
@@ -1411,8 +1407,7 @@ int psh_rows_nonfinite(int device, void* stream, const float* dataset, int64_t R
 int psh_smear_nonfinite(int device, void* stream, const float* dataset, int64_t R, int64_t C, int64_t T, int back, int fwd, float* out) {
     if (!dataset || !out || R < 0 || C <= 0 || T <= 0 || back < 0 || fwd < 0) return PSH_ERR_ARG;
     if (R * T >= ((int64_t)1 << 31) * 256) return PSH_ERR_UNSUPPORTED;
-    DeviceGuard g(device);
-    if (!g.ok) { snprintf(g_hip_err, sizeof(g_hip_err), "hipSetDevice(%d) failed", device); return PSH_ERR_HIP; }
+    GUARD_DEVICE(device);
     HIP_TRY(launch_smear_nonfinite(dataset, R, C, T, back, fwd, out, (hipStream_t)stream));
     return PSH_OK;
 }
@@ -1420,8 +1415,7 @@ int psh_smear_nonfinite(int device, void* stream, const float* dataset, int64_t 
 int psh_weighted_moments(int device, void* stream, const float* values, const double* weights, int B, int k, int m,
                          double* out_mean, double* out_std) {
     if (!values || !out_mean || !out_std || B <= 0 || k <= 0 || m <= 0) return PSH_ERR_ARG;
-    DeviceGuard g(device);
-    if (!g.ok) { snprintf(g_hip_err, sizeof(g_hip_err), "hipSetDevice(%d) failed", device); return PSH_ERR_HIP; }
+    GUARD_DEVICE(device);
     MomentsArgs a{values, weights, B, k, m, out_mean, out_std};
     HIP_TRY(launch_moments(a, (hipStream_t)stream));
     return PSH_OK;
@@ -1432,8 +1426,7 @@ int psh_realized_variance(int device, void* stream, const float* x, int64_t n_ro
     if (!x || !Ts || !out || n_rows < 0 || len <= 0 || row_stride < len || nT <= 0) return PSH_ERR_ARG;
     if (nT > PSH_RV_MAX_T) return PSH_ERR_UNSUPPORTED;
     if (n_rows == 0) return PSH_OK;
-    DeviceGuard g(device);
-    if (!g.ok) { snprintf(g_hip_err, sizeof(g_hip_err), "hipSetDevice(%d) failed", device); return PSH_ERR_HIP; }
+    GUARD_DEVICE(device);
     RvArgs a{};
     a.x = x; a.n_rows = n_rows; a.row_stride = row_stride; a.nT = nT; a.vol = vol ? 1 : 0; a.out = out;
     for (int i = 0; i < nT; ++i) {
@@ -1467,8 +1460,7 @@ int psh_hedged_mc(int device, void* stream, const float* dlnx, int64_t row_strid
         a.Ms[i] = Ms[i];
     }
     a.price = out_price; a.iv = out_iv; a.strike = out_strike; a.sigma = out_sigma; a.status = out_status;
-    DeviceGuard g(device);
-    if (!g.ok) { snprintf(g_hip_err, sizeof(g_hip_err), "hipSetDevice(%d) failed", device); return PSH_ERR_HIP; }
+    GUARD_DEVICE(device);
     HIP_TRY(launch_hedged_mc(a, (hipStream_t)stream));
     return PSH_OK;
 }
@@ -1494,8 +1486,7 @@ int psh_pdv_generate(int device, void* stream, int B, int64_t S, int n_steps, co
     a.key0 = (uint32_t)seed; a.key1 = (uint32_t)(seed >> 32);
     a.R10 = R10; a.R20 = R20; a.draws = draws;
     a.sigma = out_sigma; a.St = out_St; a.dlnx = out_dlnx; a.raw = out_draws; a.dw = out_dw;
-    DeviceGuard g(device);
-    if (!g.ok) { snprintf(g_hip_err, sizeof(g_hip_err), "hipSetDevice(%d) failed", device); return PSH_ERR_HIP; }
+    GUARD_DEVICE(device);
     HIP_TRY(launch_pdv(a, (hipStream_t)stream));
     return PSH_OK;
 }
@@ -1514,8 +1505,7 @@ int psh_mrw_generate(int device, void* stream, int64_t R, int n, double sigma, c
     a.sigma = sigma; a.c0 = c0; a.key0 = (uint32_t)seed; a.key1 = (uint32_t)(seed >> 32);
     a.a_omega = a_omega; a.a_eps = a_eps;
     a.dlnx = out_dlnx; a.dlnx_stride = dlnx_row_stride; a.lnx = out_lnx; a.omega = out_omega;
-    DeviceGuard g(device);
-    if (!g.ok) { snprintf(g_hip_err, sizeof(g_hip_err), "hipSetDevice(%d) failed", device); return PSH_ERR_HIP; }
+    GUARD_DEVICE(device);
     HIP_TRY(launch_mrw(a, (hipStream_t)stream));
     return PSH_OK;
 }
@@ -1535,8 +1525,7 @@ int psh_smrw_generate(int device, void* stream, int64_t R, int n, int m, double 
     a.sigma = sigma; a.cv = c0 + v; a.key0 = (uint32_t)seed; a.key1 = (uint32_t)(seed >> 32);
     a.a_omega = a_omega; a.k_hat = (const double2*)k_hat;
     a.dlnx = out_dlnx; a.dlnx_stride = dlnx_row_stride; a.lnx = out_lnx; a.logvol = out_logvol;
-    DeviceGuard g(device);
-    if (!g.ok) { snprintf(g_hip_err, sizeof(g_hip_err), "hipSetDevice(%d) failed", device); return PSH_ERR_HIP; }
+    GUARD_DEVICE(device);
     HIP_TRY(launch_smrw(a, (hipStream_t)stream));
     return PSH_OK;
 }
