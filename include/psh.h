@@ -599,6 +599,31 @@ int psh_smrw_generate(int device, void* stream, int64_t R, int n, int m, double 
                       const double* k_hat, double c0, double v, uint64_t seed, float* out_dlnx, int64_t dlnx_row_stride,
                       double* out_lnx, double* out_logvol);
 
+/*
+ * The stylised facts of an ensemble where it lies: lagged cross-moments of (x, x^2) with itself.  x: device float32, row r
+ * starts at x + r * row_stride and holds n samples (the (R, 1, n) tensors of the generators and a scan dataset are read in
+ * place);  m: the largest lag, 0 <= m <= min(n - 1, 1024);  G: row groups, 1 <= G <= R, group g holding rows
+ * [floor(g R / G), floor((g+1) R / G)).  For each group and each lag tau = 0 .. m, the sums over the group's rows and over
+ * t = 0 .. n - 1 - tau (pairs never cross a row) of
+ *   xx = x[t] x[t+tau],   xx2 = x[t] x[t+tau]^2,   x2x = x[t]^2 x[t+tau],   x2x2 = x[t]^2 x[t+tau]^2
+ * with every sample converted to double first, all products and sums in double.
+ *   out_sums: device G x 4 x (m + 1) float64, (xx, xx2, x2x, x2x2) in that order;  out_rows_used: device G int64;
+ *   out_status: device int32 (PSH_MOMENTS_STATUS_*), or NULL;  workspace: device, psh_lagged_moments_workspace_bytes.
+ * A row that holds a NaN or an inf contributes nothing, is not counted in out_rows_used, and sets
+ * PSH_MOMENTS_STATUS_ROWS_EXCLUDED.  The summation order is fixed by (R, n, m, G) alone (no floating-point atomics, no
+ * dependence on the number of workgroups that ran): two calls give identical bits.
+ * A NULL pointer, R < 1, n < 1, row_stride < n, m < 0, m >= n, G < 1 or G > R: PSH_ERR_ARG before anything touches the
+ * device; m > 1024 or R >= 2^31: PSH_ERR_UNSUPPORTED; a workspace that is too small: PSH_ERR_WORKSPACE.
+ * The method, in full, heads shadowing_amd/csrc/psh_moments.hip; shadowing_amd/stylized.py is its numpy twin.
+ */
+#define PSH_MOMENTS_STATUS_OK             0
+#define PSH_MOMENTS_STATUS_ROWS_EXCLUDED  1   /* at least one row held a NaN or an inf and was left out */
+/* host only, nothing is launched: the bytes psh_lagged_moments needs for these sizes */
+int psh_lagged_moments_workspace_bytes(int64_t R, int m, int64_t G, size_t* out_bytes);
+int psh_lagged_moments(int device, void* stream, const float* x, int64_t R, int64_t row_stride, int n, int m, int64_t G,
+                       double* out_sums, int64_t* out_rows_used, int32_t* out_status, void* workspace,
+                       size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,10 +11,12 @@ from .path_embedding import (ArrayType, ContextManagerBase, CrossChannelContext,
                              ImputationContext, PathEmbedding, PredictionContext)
 from .path_shadowing import PathShadowing, PendingShadow, select_cartesian_product
 from .plotting import plot_closest, plot_shadow, plot_volatility
-from .mrw import MRWGenerator, SMRWGenerator, mrw_log_returns, smrw_kernel, smrw_leverage, smrw_log_returns
+from .mrw import (MRWGenerator, SMRWGenerator, mrw_log_returns, smrw_kernel, smrw_leverage, smrw_log_returns,
+                  smrw_sq_moment)
 from .pdv import AutoregressiveLinearPredictor, PDVModel, PDVModelDiscrete
 from .pricing import PriceData, Smile, compute_smile
 from .statistics import realized_variance
+from .stylized import LaggedMoments, fit_smrw, lagged_moments
 
 __all__ = [
     "ArrayType", "ContextManagerBase", "PredictionContext", "ImputationContext", "CrossChannelContext",
@@ -23,5 +25,6 @@ __all__ = [
     "plot_closest", "plot_shadow", "plot_volatility", "PriceData", "Smile", "compute_smile",
     "PDVModel", "PDVModelDiscrete", "AutoregressiveLinearPredictor",
     "MRWGenerator", "mrw_log_returns", "SMRWGenerator", "smrw_log_returns", "smrw_kernel", "smrw_leverage",
+    "smrw_sq_moment", "LaggedMoments", "lagged_moments", "fit_smrw",
 ]
 __version__ = "0.1.0"

@@ -48,7 +48,8 @@ EXPORTS = ("psh_version", "psh_strerror", "psh_last_hip_error", "psh_workspace_b
            "psh_embedded_supported", "psh_embed_plan_offset", "psh_candidates_layout", "psh_workspace_init", "psh_last_comm_error", "psh_comm_unique_id", "psh_comm_create",
            "psh_comm_destroy", "psh_comm_world", "psh_exchange_merge", "psh_stream_create_reserving", "psh_stream_destroy",
            "psh_weighted_moments", "psh_realized_variance", "psh_count_nonfinite", "psh_smear_nonfinite", "psh_rows_nonfinite",
-           "psh_shadow_block_layout", "psh_shadow_blocking", "psh_hedged_mc", "psh_pdv_generate", "psh_mrw_generate", "psh_smrw_generate")
+           "psh_shadow_block_layout", "psh_shadow_blocking", "psh_hedged_mc", "psh_pdv_generate", "psh_mrw_generate", "psh_smrw_generate",
+           "psh_lagged_moments", "psh_lagged_moments_workspace_bytes")
 
 _lib = None
 
@@ -160,6 +161,10 @@ def load() -> C.CDLL:
     L.psh_smrw_generate.restype = i32
     L.psh_smrw_generate.argtypes = [i32, vp, i64, i32, i32, C.c_double, vp, vp, C.c_double, C.c_double, C.c_uint64, vp, i64,
                                     vp, vp]
+    L.psh_lagged_moments_workspace_bytes.restype = i32
+    L.psh_lagged_moments_workspace_bytes.argtypes = [i64, i32, i64, C.POINTER(C.c_size_t)]
+    L.psh_lagged_moments.restype = i32
+    L.psh_lagged_moments.argtypes = [i32, vp, vp, i64, i64, i32, i32, i64, vp, vp, vp, vp, C.c_size_t]
     L.psh_gather_paths.restype = i32
     L.psh_gather_paths.argtypes = [i32, vp, vp, i64, i64, i64, i64, vp, i64, i32, vp]
     if L.psh_version() != PSH_VERSION:
@@ -956,6 +961,43 @@ def realized_variance(x: torch.Tensor, Ts, vol: bool = False) -> torch.Tensor | 
     _check(load().psh_realized_variance(x.device.index, _stream_ptr(x.device), x.data_ptr(), n_rows, row_stride, L, arr, len(Ts),
                                         1 if vol else 0, out.data_ptr()), "psh_realized_variance")
     return out
+
+
+PSH_MOMENTS_MAX_LAG = 1024
+PSH_MOMENTS_STATUS_ROWS_EXCLUDED = 1
+
+
+def lagged_moments_workspace_bytes(R: int, m: int, G: int) -> int:
+    out = C.c_size_t(0)
+    _check(load().psh_lagged_moments_workspace_bytes(int(R), int(m), int(G), C.byref(out)), "psh_lagged_moments_workspace_bytes")
+    return out.value
+
+
+def lagged_moments(x: torch.Tensor, m: int, G: int):
+    """psh_lagged_moments on a float32 HIP tensor (..., n) whose rows lie a constant stride apart (contiguous, a (R, 1, n)
+    ensemble, or a slice of the last dimension of one -- no copy): (sums (G, 4, m + 1) float64, rows_used (G,) int64,
+    status (1,) int32), all on the device; nothing is synchronised here."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise NativeLibraryError(f"x must be a tensor on a HIP device (got {type(x).__name__} on "
+                                 f"{getattr(x, 'device', '?')}); there is no CPU path here")
+    if x.dtype != torch.float32:
+        raise TypeError(f"x must be torch.float32, got {x.dtype}")
+    rows = _uniform_rows(x) if x.numel() else None
+    if rows is None:
+        raise ValueError("x must be non-empty rows of samples a constant stride apart, the last dimension contiguous")
+    R, row_stride = rows
+    n = x.shape[-1]
+    sums = torch.empty((int(G), 4, int(m) + 1), dtype=torch.float64, device=x.device)
+    rows_used = torch.empty((int(G),), dtype=torch.int64, device=x.device)
+    status = torch.empty((1,), dtype=torch.int32, device=x.device)
+    L = load()
+    nbytes = C.c_size_t(0)
+    _check(L.psh_lagged_moments_workspace_bytes(R, int(m), int(G), C.byref(nbytes)), "psh_lagged_moments_workspace_bytes")
+    ws = torch.empty((max(nbytes.value, 8) + 7) // 8, dtype=torch.int64, device=x.device)
+    _check(L.psh_lagged_moments(x.device.index, _stream_ptr(x.device), x.data_ptr(), R, row_stride, n, int(m), int(G),
+                                sums.data_ptr(), rows_used.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel() * 8),
+           "psh_lagged_moments")
+    return sums, rows_used, status
 
 
 def hedged_mc(dlnx: torch.Tensor, weights: torch.Tensor | None, Ts, Ms, x_init: float = 100.0, rate: float = 0.0,

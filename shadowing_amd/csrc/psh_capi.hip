@@ -1530,4 +1530,40 @@ int psh_smrw_generate(int device, void* stream, int64_t R, int n, int m, double 
     return PSH_OK;
 }
 
+// the argument checks of both psh_lagged_moments entry points, and the plan (units, lags per lane) for the sizes
+static int lagged_moments_plan(int64_t R, int m, int64_t G, MomentsLagArgs* a, size_t* bytes) {
+    if (R < 1 || m < 0 || G < 1 || G > R) return PSH_ERR_ARG;
+    if (m > PSH_MOMENTS_MAX_LAG || R >= ((int64_t)1 << 31)) return PSH_ERR_UNSUPPORTED;   // (g * R stays in int64)
+    moments_lag_plan(R, G, m, a);
+    const int64_t units = G * a->upg;
+    if (units >= ((int64_t)1 << 31)) return PSH_ERR_UNSUPPORTED;                          // (one workgroup per unit)
+    *bytes = (size_t)units * (4 * (size_t)(m + 1) * sizeof(double) + sizeof(int64_t));
+    return PSH_OK;
+}
+
+int psh_lagged_moments_workspace_bytes(int64_t R, int m, int64_t G, size_t* out_bytes) {
+    if (!out_bytes) return PSH_ERR_ARG;
+    MomentsLagArgs a{};
+    return lagged_moments_plan(R, m, G, &a, out_bytes);
+}
+
+int psh_lagged_moments(int device, void* stream, const float* x, int64_t R, int64_t row_stride, int n, int m, int64_t G,
+                       double* out_sums, int64_t* out_rows_used, int32_t* out_status, void* workspace,
+                       size_t workspace_bytes) {
+    if (!x || !out_sums || !out_rows_used || !workspace || n < 1 || row_stride < n || m >= n) return PSH_ERR_ARG;
+    MomentsLagArgs a{};
+    size_t need = 0;
+    const int rc = lagged_moments_plan(R, m, G, &a, &need);
+    if (rc != PSH_OK) return rc;
+    if (R > INT64_MAX / row_stride) return PSH_ERR_ARG;
+    if (workspace_bytes < need) return PSH_ERR_WORKSPACE;
+    a.x = x; a.R = R; a.stride = row_stride; a.G = G; a.n = n; a.m = m;
+    a.partial = (double*)workspace;
+    a.unit_rows = (int64_t*)(a.partial + G * a.upg * 4 * (int64_t)(m + 1));
+    a.out = out_sums; a.rows_used = out_rows_used; a.status = out_status;
+    GUARD_DEVICE(device);
+    HIP_TRY(launch_lagged_moments(a, (hipStream_t)stream));
+    return PSH_OK;
+}
+
 }  // extern "C"

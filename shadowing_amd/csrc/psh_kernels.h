@@ -450,4 +450,21 @@ struct SmrwArgs {
 };
 hipError_t launch_smrw(const SmrwArgs& a, hipStream_t s);
 
+// psh_moments.hip: lagged cross-moments of (x, x^2) over groups of rows (psh_lagged_moments)
+#define PSH_MOMENTS_MAX_LAG 1024
+struct MomentsLagArgs {
+    const float* x;           // R rows of n samples, stride floats apart
+    int64_t R, stride, G;     // group g holds rows [floor(g R / G), floor((g+1) R / G))
+    int n, m;                 // lags 0 .. m
+    int64_t ru, upg;          // rows per unit, units per group (moments_lag_plan: functions of R and G alone)
+    int lanes_u, chunks;      // lags per lane, lag chunks of 64 * lanes_u per workgroup (functions of m alone)
+    double* partial;          // workspace: (G * upg, 4, m + 1) ...
+    int64_t* unit_rows;       // ... then (G * upg) rows used
+    double* out;              // (G, 4, m + 1)
+    int64_t* rows_used;       // (G)
+    int32_t* status;          // PSH_MOMENTS_STATUS_*, or nullptr
+};
+void moments_lag_plan(int64_t R, int64_t G, int m, MomentsLagArgs* a);
+hipError_t launch_lagged_moments(const MomentsLagArgs& a, hipStream_t s);
+
 }  // namespace psh

@@ -15,6 +15,7 @@ psh_mrw_generate, which keeps the transform in LDS and therefore takes n <= 4096
 The skewed MRW (Pochart, Bouchaud 2002; smrw_log_returns, SMRWGenerator, smrw_leverage) adds the leverage effect: the
 log-volatility becomes omega[t] - sum_{j=1..m} K0 / j^alpha eps[t-j] at white noise, which makes E[r_t r_{t+tau}^2]
 negative and the smile skewed.  Its statement heads shadowing_amd/csrc/psh_smrw.hip; `cuda=True` runs psh_smrw_generate.
+smrw_sq_moment is E[r_t^2 r_{t+tau}^2] in closed form; stylized.fit_smrw fits both closed forms to a measured ensemble.
 """
 from __future__ import annotations
 
@@ -292,6 +293,26 @@ def smrw_leverage(tau: int, n: int, K0: float, alpha: float, lam: float = 0.2, L
     return -2.0 * float(K[tau - 1]) * sigma ** 3 * math.exp(0.5 * S + 2.0 * ct - 0.5 * c0 - 3.0 * v)
 
 
+def smrw_sq_moment(tau: int, n: int, K0: float, alpha: float, lam: float = 0.2, L: float | None = None,
+                   memory: int | None = None, sigma: float = DEFAULT_SIGMA) -> float:
+    """E[r_t^2 r_{t+tau}^2] of the skewed MRW in closed form, 1 <= tau (K(j) = 0 past the memory):
+        sigma^4 (1 + 4 K(tau)^2) exp(4 c[tau] + 2 K(tau)^2 + 2 sum_{j>=1} (K(j) + K(j + tau))^2 + 2 sum_{j<tau} K(j)^2 - 4 v)
+    (the exponent 2 lv[t] + 2 lv[t+tau] is Gaussian; eps[t] enters it with coefficient -2 K(tau) and
+    E[e^2 exp(a e)] = (1 + a^2) exp(a^2 / 2); eps[t+tau] is independent of it).  sigma^4 exp(4 c[tau]) at K0 = 0: the
+    volatility clustering of the MRW.  With smrw_leverage, what fit_smrw fits a measured ensemble against."""
+    n, lam, L, m, sigma, K = _check_smrw(n, K0, alpha, 0.5, lam, L, memory, sigma)
+    if isinstance(tau, bool) or int(tau) != tau or tau < 1:
+        raise ValueError(f"tau must be an integer >= 1, got {tau!r}")
+    tau = int(tau)
+    shifted = np.zeros(m)
+    if tau < m:
+        shifted[:m - tau] = K[tau:]                                      # K(j + tau), 0 past the memory
+    Kt = float(K[tau - 1]) if tau <= m else 0.0
+    ct, v = float(mrw_covariance(tau, L, lam)), float(np.sum(K ** 2))
+    expo = 4.0 * ct + 2.0 * Kt ** 2 + 2.0 * float(np.sum((K + shifted) ** 2)) + 2.0 * float(np.sum(K[:min(tau - 1, m)] ** 2)) - 4.0 * v
+    return sigma ** 4 * (1.0 + 4.0 * Kt ** 2) * math.exp(expo)
+
+
 def _smrw_host(R: int, n: int, K: np.ndarray, lam: float, L: float, sigma: float, seed: int, first_path: int = 0):
     """The numpy twin of psh_smrw_generate: (r, lv), both (R, n) float64, of paths first_path .. first_path + R - 1."""
     key = (seed & 0xFFFFFFFF, seed >> 32)
@@ -385,4 +406,4 @@ class SMRWGenerator:
 
 
 __all__ = ["MRWGenerator", "mrw_log_returns", "mrw_spectrum", "fgn_spectrum", "mrw_covariance", "fgn_covariance",
-           "SMRWGenerator", "smrw_log_returns", "smrw_kernel", "smrw_leverage", "MAX_N_DEVICE", "DEFAULT_SIGMA"]
+           "SMRWGenerator", "smrw_log_returns", "smrw_kernel", "smrw_leverage", "smrw_sq_moment", "MAX_N_DEVICE", "DEFAULT_SIGMA"]
