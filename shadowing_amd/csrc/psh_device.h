@@ -1,6 +1,7 @@
 // psh_device.h -- device code shared by the translation units of libpsh_hip.so (psh_scan.hip, psh_embed.hip,
 // psh_select.hip): small helpers, the per-query preparation, the per-lane window arithmetic of the scans, the
-// staging of a segment, the deferred candidate append.  Internal; see psh_scan.hip for the design overview.
+// deferred candidate append.  The staging of a segment, the scan kernels' unit queue and the one-query matrix-core
+// segment test are in psh_segment.h.  Internal; see psh_scan.hip for the design overview.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -32,6 +33,21 @@ __device__ __forceinline__ unsigned fast_div(unsigned u, unsigned magic, unsigne
     unsigned q = __umulhi(u, magic);
     q += (u - q * d >= d) ? 1u : 0u;
     return q;
+}
+
+// Words exchanged between blocks or launches (psh_fused.hip, psh_stream.hip): an agent-scope relaxed atomic store is a
+// write-through (sc1) store; bulk reads are sc1 BUFFER loads (aux bit 4), which bypass L1 like an atomic load.
+typedef unsigned long long u64;
+typedef __attribute__((address_space(1))) u64 gu64;
+typedef __attribute__((address_space(1))) unsigned gu32;
+typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
+#define PSH_AUX_SC1 16
+__device__ __forceinline__ void store_sc1(unsigned* p, unsigned v) {
+    __hip_atomic_store((gu32*)(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// a raw buffer resource over `bytes` bytes at `base`: reads past the end return zero
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_rsrc(const void* base, unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
 }
 
 // LDS tile layout: logical float p lives at p + 4*(p/64): one 16-byte pad slot after
@@ -364,6 +380,11 @@ __device__ __forceinline__ float wave_sum_dpp(float x) {
     const float r2 = __int_as_float(__builtin_amdgcn_readlane(v, 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(v, 48));
     return (r0 + r1) + (r2 + r3);
 }
+// inc += (inc of the lane CTRL names, 0 where there is none): one step of a wave scan, a v_add_f32 with a DPP operand
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ float dpp_add(float inc) {
+    return inc + __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(inc), CTRL, ROW_MASK, 0xf, true));
+}
 __device__ __forceinline__ float max3f(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }   // v_max3_f32, as above
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
 __device__ __forceinline__ float tile_min16(const f32x16_t& t) {
@@ -380,71 +401,6 @@ __device__ __forceinline__ float min16(const float (&a)[PSH_L]) {
 #pragma unroll
     for (int i = 3; i + 1 < PSH_L; i += 2) m = fminf(fminf(m, a[i]), a[i + 1]);
     return fminf(m, a[PSH_L - 1]);
-}
-
-struct Stage {  // one segment in flight from HBM, 5 x 16 bytes per lane
-    f32x4 v[PSH_NSTAGE];
-};
-
-// one of the PSH_NSTAGE 16-byte loads of a segment (q is a compile-time index at every
-// call site).  row: first float of the row; floats [seg_start, seg_start + nfloat) are
-// wanted, clamped to the row (the clamped tail only feeds inadmissible windows).
-template <bool ALIGNED>
-__device__ __forceinline__ void stage_load_one(Stage& st, int q, const float* __restrict__ row, int64_t T,
-                                               int seg_start, int nfloat, int lane) {
-    if (ALIGNED) {
-        const f32x4* src = reinterpret_cast<const f32x4*>(row + seg_start);
-        const int last = (int)((T - seg_start) >> 2) - 1;  // last float4 inside the row
-        const int nq = (nfloat + 3) >> 2;                   // 256 <= nq <= 320
-        int m = lane + 64 * q;
-        if (q < PSH_NSTAGE - 1 || m < nq) {
-            m = m > last ? last : m;
-            st.v[q] = __builtin_nontemporal_load(src + m);
-        }
-    } else {
-        const int lastf = (int)(T - seg_start) - 1;
-        float e[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            int p = 4 * (lane + 64 * q) + c;
-            p = p > lastf ? lastf : p;
-            e[c] = (4 * (lane + 64 * q) < nfloat) ? row[seg_start + p] : 0.0f;
-        }
-        st.v[q] = f32x4{e[0], e[1], e[2], e[3]};
-    }
-}
-
-template <bool ALIGNED>
-__device__ __forceinline__ void stage_load(Stage& st, const float* __restrict__ row, int64_t T,
-                                           int seg_start, int nfloat, int lane) {
-#pragma unroll
-    for (int q = 0; q < PSH_NSTAGE; ++q) stage_load_one<ALIGNED>(st, q, row, T, seg_start, nfloat, lane);
-}
-
-template <bool PAD = true>
-__device__ __forceinline__ void stage_store(const Stage& st, float* tile, int nfloat, int lane) {
-    const int nq = (nfloat + 3) >> 2;
-#pragma unroll
-    for (int q = 0; q < PSH_NSTAGE; ++q) {
-        const int m = lane + 64 * q;
-        if (q < PSH_NSTAGE - 1 || m < nq) *reinterpret_cast<f32x4*>(tile + lds_idx<PAD>(4 * m)) = st.v[q];
-    }
-}
-
-// ---- matrix-core rejection test: f16 staging layout (scan_mx_kernel, scan_mq_kernel, scan_fused_kernel) ---------
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-#define PSH_MX_SLOTS 144                      // 16-byte slots per f16 array: 32*31 + 64 values, whole groups of 16 slots
-#define PSH_MX_NHALF (PSH_MX_SLOTS * 8)
-#define PSH_MX_PEND 64                        // >= 64: one ballot can admit a whole wave
-
-// logical f16 index -> LDS index.  A-fragment reads of the 32 rows sit 64 bytes apart
-// (4 slots): rotating the slot inside its group of 16 by the group number spreads 16
-// consecutive rows over 16 distinct slots without any padding.
-__device__ __forceinline__ int mx_half(int idx) {
-    const int slot = idx >> 3;
-    return (((slot & ~15) | ((slot + (slot >> 4)) & 15)) << 3) | (idx & 7);
 }
 
 // A call that reports PSH_STATUS_RETRY leaves NO plausible numbers behind: NaN distances and (-1, -1) indices instead of an

@@ -1,7 +1,7 @@
 // psh_embed.hip -- the scans behind a linear embedding (embed_scan_kernel: dense fma chains, and the suffix-rows
 // rejection test for Foveal-like kernels) and over one-window rows (rows_kernel: PathDistance.forward_topk), with their
-// launchers.  Part of libpsh_hip.so; shared device code in psh_device.h, design overview at the top of psh_scan.hip.
-#include "psh_device.h"
+// launchers.  Part of libpsh_hip.so; shared device code in psh_device.h / psh_segment.h, design overview at the top of psh_scan.hip.
+#include "psh_segment.h"
 
 namespace psh {
 
@@ -343,24 +343,18 @@ __global__ __launch_bounds__(THREADS) void embed_scan_kernel(ScanArgs a) {
 
     const int nfloat = PSH_SEG + K - 1;
     const unsigned n_rs = (unsigned)a.n_rows * (unsigned)a.nseg;
-    const unsigned n_units = n_rs * (unsigned)a.n_qgroups;
-    const unsigned u_lo = (unsigned)(((unsigned long long)n_units * blockIdx.x) / gridDim.x);
-    const unsigned u_hi = (unsigned)(((unsigned long long)n_units * (blockIdx.x + 1)) / gridDim.x);
+    const UnitQueue uq = unit_queue(n_rs * (unsigned)a.n_qgroups, next_unit);
     const const_f32p hxk = (const_f32p)a.hx;
     typedef const __attribute__((address_space(4))) QueryState* const_qsp;
     const const_qsp qstate_k = (const_qsp)a.qstate;
 
     for (;;) {
-        int v = 0;
-        if (lane == 0) v = atomicAdd(next_unit, 1);
-        const unsigned u = u_lo + (unsigned)__builtin_amdgcn_readfirstlane(v);
-        if (u >= u_hi) break;
-        const unsigned qgi = fast_div(u, a.magic_nrs, n_rs);
-        const unsigned rs = u - qgi * n_rs;
-        const unsigned ri = fast_div(rs, a.magic_nseg, (unsigned)a.nseg);
-        const unsigned sg = rs - ri * (unsigned)a.nseg;
-        const int64_t row = a.row0 + (int64_t)ri * a.row_stride;
-        const int seg_start = (int)sg * PSH_SEG;
+        const unsigned u = uq.grab(lane);
+        if (u >= uq.hi) break;
+        const Unit c = unit_decode(a, u, n_rs);
+        const unsigned qgi = c.qg, rs = c.rs;
+        const int64_t row = c.row(a);
+        const int seg_start = c.seg_start();
 
         if (MODE == PSH_MODE_FILTER && npend > 0) {   // stores ahead of the loads: vmcnt retires in order
             pend_flush(pend, npend, lcount, a, lane);
@@ -369,7 +363,7 @@ __global__ __launch_bounds__(THREADS) void embed_scan_kernel(ScanArgs a) {
         float ymax = 0.0f;
         {
             Stage st;
-            stage_load<ALIGNED>(st, a.dataset + row * a.T, a.T, seg_start, nfloat, lane);
+            load_unit<ALIGNED>(st, a, c, nfloat, lane);
             if (MODE != PSH_MODE_ALL && nested) {            // max |y| of everything this segment reads (NaN ignored: see above)
 #pragma unroll
                 for (int q = 0; q < PSH_NSTAGE; ++q) {

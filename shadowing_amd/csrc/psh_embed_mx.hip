@@ -43,7 +43,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "psh_device.h"
+#include "psh_segment.h"
 
 namespace psh {
 
@@ -303,9 +303,7 @@ __global__ __launch_bounds__(PSH_EMX_THREADS) void embed_mx_kernel(ScanArgs a) {
 
     const int nfloat = PSH_SEG + K - 1;
     const unsigned n_rs = (unsigned)a.n_rows * (unsigned)a.nseg;
-    const unsigned n_units = n_rs * (unsigned)a.n_qgroups;
-    const unsigned u_lo = (unsigned)(((unsigned long long)n_units * blockIdx.x) / gridDim.x);
-    const unsigned u_hi = (unsigned)(((unsigned long long)n_units * (blockIdx.x + 1)) / gridDim.x);
+    const UnitQueue uq = unit_queue(n_rs * (unsigned)a.n_qgroups, &ctl[0]);
     const const_f32p hxk = (const_f32p)a.hx;
     typedef const __attribute__((address_space(4))) QueryState* const_qsp;
     const const_qsp qstate_k = (const_qsp)a.qstate;
@@ -323,9 +321,9 @@ __global__ __launch_bounds__(PSH_EMX_THREADS) void embed_mx_kernel(ScanArgs a) {
     // the last one to three survivors wait for the next units' (a pass costs the same 6 - 8 k cycles for one survivor as for
     // four, and a unit finds 0.5 on average -- 0.41 passes per unit became 0.13); the last unit of the wave flushes.
     auto coords = [&](unsigned rsu, int& seg_start_e, int64_t& row_e) {
-        const unsigned ri2 = fast_div(rsu, a.magic_nseg, (unsigned)a.nseg);
-        seg_start_e = (int)(rsu - ri2 * (unsigned)a.nseg) * PSH_SEG;
-        row_e = a.row0 + (int64_t)ri2 * a.row_stride;
+        const Unit ce = unit_decode(a, rsu);
+        seg_start_e = ce.seg_start();
+        row_e = ce.row(a);
     };
     auto verify_impl = [&](bool whole_passes_only, auto fast_c) {
         constexpr bool FAST = decltype(fast_c)::value;
@@ -447,18 +445,9 @@ __global__ __launch_bounds__(PSH_EMX_THREADS) void embed_mx_kernel(ScanArgs a) {
     auto verify = [&]() { verify_impl(false, std::false_type{}); };
     auto verify_end = [&](bool whole_passes_only) { verify_impl(whole_passes_only, std::true_type{}); };
 
-    auto grab = [&]() -> unsigned {
-        int v0 = 0;
-        if (lane == 0) v0 = atomicAdd(&ctl[0], 1);
-        return u_lo + (unsigned)__builtin_amdgcn_readfirstlane(v0);
-    };
-    auto load_unit = [&](Stage& sx, unsigned uu) {
-        const unsigned qg2 = fast_div(uu, a.magic_nrs, n_rs);
-        const unsigned rs2 = uu - qg2 * n_rs;
-        const unsigned ri2 = fast_div(rs2, a.magic_nseg, (unsigned)a.nseg);
-        const unsigned sg2 = rs2 - ri2 * (unsigned)a.nseg;
+    auto load_next = [&](Stage& sx, unsigned uu) {
         sx.v[PSH_NSTAGE - 1] = f32x4{0.f, 0.f, 0.f, 0.f};  // (the last, partial stage: lanes past the segment would otherwise KEEP the old one -- live across the unit)
-        stage_load<ALIGNED>(sx, a.dataset + (a.row0 + (int64_t)ri2 * a.row_stride) * a.T, a.T, (int)sg2 * PSH_SEG, nfloat, lane);
+        load_unit<ALIGNED>(sx, a, unit_decode(a, uu, n_rs), nfloat, lane);
     };
     // One segment in flight from HBM besides the one being worked on.  The full scan (LATE) has no 20 registers to keep it in
     // across a unit -- the compiler spilled part of it right behind the loads, i.e. WAITED for HBM twice per unit (r03: 7.6 k of a
@@ -466,27 +455,22 @@ __global__ __launch_bounds__(PSH_EMX_THREADS) void embed_mx_kernel(ScanArgs a) {
     // segment comes to the L2) and read into registers at its end, when the accumulators are dead.
     constexpr bool LATE = (MODE == PSH_MODE_FILTER && NP == 1);
     auto touch_unit = [&](unsigned uu) -> float {
-        const unsigned qg2 = fast_div(uu, a.magic_nrs, n_rs);
-        const unsigned rs2 = uu - qg2 * n_rs;
-        const unsigned ri2 = fast_div(rs2, a.magic_nseg, (unsigned)a.nseg);
-        const unsigned sg2 = rs2 - ri2 * (unsigned)a.nseg;
-        const float* rowp = a.dataset + (a.row0 + (int64_t)ri2 * a.row_stride) * a.T;
-        int p = (int)sg2 * PSH_SEG + 32 * lane;
-        const int pl = (int)sg2 * PSH_SEG + nfloat - 1;
+        const Unit cn = unit_decode(a, uu, n_rs);
+        const float* rowp = a.dataset + cn.row(a) * a.T;
+        int p = cn.seg_start() + 32 * lane;
+        const int pl = cn.seg_start() + nfloat - 1;
         p = p < pl ? p : pl;
         p = p < (int)a.T - 1 ? p : (int)a.T - 1;
         return rowp[p];
     };
     Stage st;
-    unsigned u = grab();
-    if (u < u_hi) load_unit(st, u);
-    while (u < u_hi) {
-        const unsigned qgi = fast_div(u, a.magic_nrs, n_rs);
-        const unsigned rs = u - qgi * n_rs;
-        const unsigned ri = fast_div(rs, a.magic_nseg, (unsigned)a.nseg);
-        const unsigned sg = rs - ri * (unsigned)a.nseg;
-        const int64_t row = a.row0 + (int64_t)ri * a.row_stride;
-        const int seg_start = (int)sg * PSH_SEG;
+    unsigned u = uq.grab(lane);
+    if (u < uq.hi) load_next(st, u);
+    while (u < uq.hi) {
+        const Unit c = unit_decode(a, u, n_rs);
+        const unsigned qgi = c.qg, rs = c.rs;
+        const int64_t row = c.row(a);
+        const int seg_start = c.seg_start();
         const int r_global = (int)(row + a.r_offset);
 
         // ---- the segment: fp32 tile (verification), scale, hi/lo f16 copies
@@ -521,11 +505,11 @@ __global__ __launch_bounds__(PSH_EMX_THREADS) void embed_mx_kernel(ScanArgs a) {
                 pend_flush(pend, npend, lcount, a, lane);
                 npend = 0;
             }
-            un = grab();
-            if (!LATE && un < u_hi) load_unit(st, un);
+            un = uq.grab(lane);
+            if (!LATE && un < uq.hi) load_next(st, un);
         }
         float touched = 0.0f;
-        if (LATE && un < u_hi) touched = touch_unit(un);
+        if (LATE && un < uq.hi) touched = touch_unit(un);
         wave_lds_fence();
 
         const float inv = __uint_as_float((unsigned)(127 - ey - ekc) << 23);
@@ -955,13 +939,13 @@ __global__ __launch_bounds__(PSH_EMX_THREADS) void embed_mx_kernel(ScanArgs a) {
             tstamp(2);
         }
 #ifdef PSH_TUNING
-        tcount[0] += (unsigned)(un < u_hi ? (nsq & ~3) : nsq); tcount[1] += (unsigned)(un < u_hi ? (nsq >> 2) : ((nsq + 3) >> 2));
+        tcount[0] += (unsigned)(un < uq.hi ? (nsq & ~3) : nsq); tcount[1] += (unsigned)(un < uq.hi ? (nsq >> 2) : ((nsq + 3) >> 2));
 #endif
         // (the accumulators are dead here: the register-hungry fast chain; whole passes of four while more units follow)
-        if (MODE == PSH_MODE_FILTER && (un < u_hi ? nsq >= 4 : nsq > 0)) verify_end(un < u_hi);
+        if (MODE == PSH_MODE_FILTER && (un < uq.hi ? nsq >= 4 : nsq > 0)) verify_end(un < uq.hi);
         if (LATE) {
             asm volatile("" ::"v"(touched));                                                               // (the touch has landed: one register across the unit)
-            load_unit(st, un < u_hi ? un : u);             // (unconditionally: a segment kept "as it was" would be live across the whole unit)
+            load_next(st, un < uq.hi ? un : u);             // (unconditionally: a segment kept "as it was" would be live across the whole unit)
         }
         tstamp(3);
         wave_lds_fence();

@@ -31,7 +31,7 @@
 // stage does the work -- the other one returns at once.
 #include <type_traits>
 
-#include "psh_device.h"
+#include "psh_segment.h"
 
 namespace psh {
 
@@ -259,12 +259,6 @@ hipError_t launch_embed_plan(const float* ker, int d, int K, EmbedPlan* plan, hi
     return hipGetLastError();
 }
 
-// inc += (inc of the lane CTRL names, 0 where there is none): one step of the wave scan, a v_add_f32 with a DPP operand
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_add(float inc) {
-    return inc + __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(inc), CTRL, ROW_MASK, 0xf, true));
-}
-
 // Exclusive prefix sums of the staged segment (element 4 (lane + 64 q) + r of Stage) -> dst[0 .. 4 nq]; returns the sum of
 // |y| over the staged samples (what bounds the rounding of the sums, below).
 // fp32 all the way, except the carry from one 256-sample block to the next (a double: two scalar-rate instructions a block):
@@ -370,9 +364,7 @@ __global__ __launch_bounds__(THREADS) void embed_px_kernel(ScanArgs a) {
 
     const int nfloat = PSH_SEG + K - 1;
     const unsigned n_rs = (unsigned)a.n_rows * (unsigned)a.nseg;
-    const unsigned n_units = n_rs * (unsigned)a.n_qgroups;
-    const unsigned u_lo = (unsigned)(((unsigned long long)n_units * blockIdx.x) / gridDim.x);
-    const unsigned u_hi = (unsigned)(((unsigned long long)n_units * (blockIdx.x + 1)) / gridDim.x);
+    const UnitQueue uq = unit_queue(n_rs * (unsigned)a.n_qgroups, next_unit);
     typedef const __attribute__((address_space(4))) QueryState* const_qsp;
     const const_qsp qstate_k = (const_qsp)a.qstate;
 
@@ -389,9 +381,9 @@ __global__ __launch_bounds__(THREADS) void embed_px_kernel(ScanArgs a) {
     // d = 34 -- and a unit lists one now and then), the rest waits for the next units'; the wave's last unit flushes.
     int ns = 0;                                              // survivors waiting in sl (wave-uniform)
     auto coords = [&](unsigned rsu, int& seg_start_e, int64_t& row_e) {
-        const unsigned ri2 = fast_div(rsu, a.magic_nseg, (unsigned)a.nseg);
-        seg_start_e = (int)(rsu - ri2 * (unsigned)a.nseg) * PSH_SEG;
-        row_e = a.row0 + (int64_t)ri2 * a.row_stride;
+        const Unit ce = unit_decode(a, rsu);
+        seg_start_e = ce.seg_start();
+        row_e = ce.row(a);
     };
     // Exact verification of the listed survivors (window index | query << 12), rows across the lanes: lane (el, l)
     // runs the chains of row l and then of row d-1-l of survivor el (short and long support: equal work per lane),
@@ -542,16 +534,12 @@ __global__ __launch_bounds__(THREADS) void embed_px_kernel(ScanArgs a) {
     };
 
     for (;;) {
-        int v = 0;
-        if (lane == 0) v = atomicAdd(next_unit, 1);
-        const unsigned u = u_lo + (unsigned)__builtin_amdgcn_readfirstlane(v);
-        if (u >= u_hi) break;
-        const unsigned qgi = fast_div(u, a.magic_nrs, n_rs);
-        const unsigned rs = u - qgi * n_rs;
-        const unsigned ri = fast_div(rs, a.magic_nseg, (unsigned)a.nseg);
-        const unsigned sg = rs - ri * (unsigned)a.nseg;
-        const int64_t row = a.row0 + (int64_t)ri * a.row_stride;
-        const int seg_start = (int)sg * PSH_SEG;
+        const unsigned u = uq.grab(lane);
+        if (u >= uq.hi) break;
+        const Unit c = unit_decode(a, u, n_rs);
+        const unsigned qgi = c.qg, rs = c.rs;
+        const int64_t row = c.row(a);
+        const int seg_start = c.seg_start();
 
         if (MODE == PSH_MODE_FILTER && npend > 0) {   // stores ahead of the loads: vmcnt retires in order
             pend_flush(pend, npend, lcount, a, lane);
@@ -560,7 +548,7 @@ __global__ __launch_bounds__(THREADS) void embed_px_kernel(ScanArgs a) {
         float ymax = 0.0f, asum;
         {
             Stage st;
-            stage_load<ALIGNED>(st, a.dataset + row * a.T, a.T, seg_start, nfloat, lane);
+            load_unit<ALIGNED>(st, a, c, nfloat, lane);
 #pragma unroll
             for (int q = 0; q < PSH_NSTAGE; ++q) {          // max |y| of everything this segment reads (NaN ignored)
                 if (q < PSH_NSTAGE - 1 || lane + 64 * q < ((nfloat + 3) >> 2)) {

@@ -32,19 +32,13 @@
 // (|y~| > 255) has acc~ >= (255 - 8)^2 > tau~ and is rightly rejected when its t^ comes out +inf (NaN is kept).
 // Both follow from the query and tau alone: scale = the largest power of two with max|x| * scale < 8 and
 // tau2 * scale^2 <= 4096.
-#include "psh_device.h"
+#include "psh_segment.h"
 
 namespace psh {
 
-typedef unsigned long long u64;
-typedef __attribute__((address_space(1))) u64 gu64;
-typedef __attribute__((address_space(1))) unsigned gu32;
-
+// (u64 / gu64 / gu32, store_sc1, buffer_rsrc, PSH_AUX_SC1: psh_device.h -- shared with psh_stream.hip)
 __device__ __forceinline__ void g_store(u64* p, u64 v) {
     __hip_atomic_store((gu64*)(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void g_store32(unsigned* p, unsigned v) {
-    __hip_atomic_store((gu32*)(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 // a word the HOST reads (a blocking caller's pinned block): write-through to system scope
 __device__ __forceinline__ void store32_system(unsigned* p, unsigned v) {
@@ -58,11 +52,6 @@ __device__ __forceinline__ u64 g_load(const u64* p) {
 // loads to the compiler -- it keeps them all in flight and waits once.  (A relaxed agent-scope __hip_atomic_load is
 // followed by s_waitcnt vmcnt(0) each: 8 granules per lane cost 8 serial round trips, 16 us per sweep.)
 typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
-#define PSH_AUX_SC1 16
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t g_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
 __device__ __forceinline__ u64 g_load_b64(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
     const u32x2v v = __builtin_amdgcn_raw_buffer_load_b64(r, (int)byte_off, 0, PSH_AUX_SC1);
     return ((u64)v[1] << 32) | (u64)v[0];
@@ -123,23 +112,20 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_fused_kernel(ScanArgs a
     // and the odd XCDs stream ~4 % slower than the even ones on every box measured (tools/fused_times.py: they end their
     // equal shares 2.5-4.5 us later, launch after launch): of the units of a pair of blocks (2j, 2j + 1) the even one
     // takes (256 + skew) / 512.  (Were the dealing different, the shares would merely be 2 % off.)
-    unsigned u_lo, u_hi;
+    UnitQueue uq;
     {
         const unsigned pb = blockIdx.x & ~1u;
         const unsigned p_lo = (unsigned)(((u64)n_rs * pb) / gridDim.x);
         const unsigned p_hi = (unsigned)(((u64)n_rs * (pb + 2 < gridDim.x ? pb + 2 : gridDim.x)) / gridDim.x);
         const bool paired = pb + 1 < gridDim.x;
         const unsigned mid = paired ? p_lo + (unsigned)(((u64)(p_hi - p_lo) * (unsigned)(256 + f.xcd_skew)) >> 9) : p_hi;
-        u_lo = (blockIdx.x & 1u) ? mid : p_lo;
-        u_hi = (blockIdx.x & 1u) ? p_hi : mid;
+        uq = UnitQueue{(blockIdx.x & 1u) ? mid : p_lo, (blockIdx.x & 1u) ? p_hi : mid, &ctl[C_NEXT]};
     }
 
     // the first sampled segment of every wave is requested before anything else: the header check, the LDS set-up and
     // the block barrier below run under its HBM latency
     auto boot_load = [&](Stage& sx, unsigned uu) {
-        const unsigned ri = fast_div(uu, a.magic_nseg, (unsigned)a.nseg);
-        const unsigned sg = uu - ri * (unsigned)a.nseg;
-        stage_load<ALIGNED>(sx, a.dataset + (f.boot_row0 + (int64_t)ri * f.boot_row_stride) * a.T, a.T, (int)sg * PSH_SEG, nfloat, lane);
+        load_unit<ALIGNED>(sx, a, f.boot_row0, f.boot_row_stride, unit_decode(a, uu), nfloat, lane);
     };
     constexpr bool hinted = HINTED;
     const unsigned nbu = hinted ? 0u : (unsigned)f.boot_units;
@@ -175,9 +161,7 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_fused_kernel(ScanArgs a
         unsigned u = ub;
         Stage& st = stb;
         while (u < nbu) {
-            const unsigned ri = fast_div(u, a.magic_nseg, (unsigned)a.nseg);
-            const unsigned sg = u - ri * (unsigned)a.nseg;
-            const int seg_start = (int)sg * PSH_SEG;
+            const int seg_start = unit_decode(a, u).seg_start();
             stage_store(st, tile, nfloat, lane);
             wave_lds_fence();
             const unsigned un = u + stride;
@@ -209,7 +193,7 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_fused_kernel(ScanArgs a
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) m = fminf(m, __shfl_xor(m, off, 64));
             if (!(m == m)) m = __uint_as_float(PSH_INF_BITS);                  // NaN data: the segment carries no information
-            if (lane == 0) g_store32(&hdr->minima[u], __float_as_uint(m));     // write-through; the block's flag follows the drain
+            if (lane == 0) store_sc1(&hdr->minima[u], __float_as_uint(m));     // write-through; the block's flag follows the drain
             wave_lds_fence();
             u = un;
         }
@@ -222,23 +206,9 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_fused_kernel(ScanArgs a
     }
     stamp(1);
     // the first segment of the scan is requested now: its HBM latency runs under phase B
-    auto grab = [&]() -> unsigned {
-        int v = 0;
-        if (lane == 0) v = atomicAdd(&ctl[C_NEXT], 1);
-        return u_lo + (unsigned)__builtin_amdgcn_readfirstlane(v);
-    };
-    auto decode = [&](unsigned uu, unsigned& ri, unsigned& sg) {
-        ri = fast_div(uu, a.magic_nseg, (unsigned)a.nseg);
-        sg = uu - ri * (unsigned)a.nseg;
-    };
-    auto load_unit = [&](Stage& sx, unsigned uu) {
-        unsigned ri, sg;
-        decode(uu, ri, sg);
-        stage_load<ALIGNED>(sx, a.dataset + (a.row0 + (int64_t)ri * a.row_stride) * a.T, a.T, (int)sg * PSH_SEG, nfloat, lane);
-    };
     Stage st;
-    unsigned u = grab();
-    if (u < u_hi) load_unit(st, u);
+    unsigned u = uq.grab(lane);
+    if (u < uq.hi) load_unit<ALIGNED>(st, a, unit_decode(a, u), nfloat, lane);
 
     // the admission level -> f16 scale and rejection threshold (one lane; phase B, sampled or hinted)
     auto derive_levels = [&](const float tau0) {
@@ -295,7 +265,7 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_fused_kernel(ScanArgs a
         // first barrier: wave 0 sweeps the 256 block flags (2 KB; the other 15 waves do not add to the polling traffic)
         if (wave == 0) {
             const int nblk = (int)gridDim.x;
-            const __amdgpu_buffer_rsrc_t rfl = g_rsrc(hdr->aflag, sizeof(hdr->aflag));
+            const __amdgpu_buffer_rsrc_t rfl = buffer_rsrc(hdr->aflag, sizeof(hdr->aflag));
             for (;;) {
                 bool ok = true;
                 u64 xg[PSH_FUSED_MAX_BLOCKS / 64];
@@ -316,7 +286,7 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_fused_kernel(ScanArgs a
         unsigned kmin = 0xffffffffu, kmax = 0u;
         int nfin = 0;
         {
-            const __amdgpu_buffer_rsrc_t rmin = g_rsrc(hdr->minima, sizeof(hdr->minima));
+            const __amdgpu_buffer_rsrc_t rmin = buffer_rsrc(hdr->minima, sizeof(hdr->minima));
             const u32x4v mv = __builtin_amdgcn_raw_buffer_load_b128(rmin, tid * 16, 0, PSH_AUX_SC1);
             *reinterpret_cast<u32x4v*>(keys + 4 * tid) = mv;
 #pragma unroll
@@ -404,11 +374,13 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_fused_kernel(ScanArgs a
     const float xn = __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane(ctl[C_XN]));
 
     stamp(3);
-    // ------------------------------------------------------------------ C: the scan (scan_mx_kernel's loop)
-    {   // the f16 arrays held the minima: every slot a segment does not write must be finite (0 * NaN poisons a row)
-        unsigned* z = reinterpret_cast<unsigned*>(a1);
-        for (int i = lane; i < PSH_MX_NHALF; i += 64) z[i] = 0u;              // 2 arrays x NHALF halves = NHALF dwords
-    }
+    // ------------------------------------------------------------------ C: the scan (scan_mx_kernel's loop: the segment test
+    // of psh_segment.h)
+    mx_zero(a1, lane);                                   // (the f16 arrays held the minima)
+    // The two bands in ONE loop and the A fragments read in place, not through mx_band_query / mx_band_ones / mx_load_a:
+    // this kernel sits at the 128-register cap.  With the bands as two loops their 32 masks stay live from one to the
+    // other (8 to 25 more spilled SGPRs in every instantiation, a spilled VGPR in one); with mx_load_a the two aligned
+    // sampled BLK instantiations went from 117 / 119 to 128 VGPRs and a spill.  (Compiler output only: not timed.)
     f16x8 bx[4], bo[4];
     {
         const int n = lane & 31, hk = lane >> 5;
@@ -424,37 +396,23 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_fused_kernel(ScanArgs a
             }
     }
     wave_lds_fence();
-    while (u < u_hi) {
-        unsigned ri, sg;
-        decode(u, ri, sg);
-        const int64_t row = a.row0 + (int64_t)ri * a.row_stride;
-        const int seg_start = (int)sg * PSH_SEG;
-        const int r_global = (int)(row + a.r_offset);
+    while (u < uq.hi) {
+        const Unit c = unit_decode(a, u);
+        const int seg_start = c.seg_start();
+        const int r_global = (int)(c.row(a) + a.r_offset);
 
         stage_store(st, tile, nfloat, lane);
-        {
-            const int nq = (nfloat + 3) >> 2;
-#pragma unroll
-            for (int q = 0; q < PSH_NSTAGE; ++q) {
-                const int m = lane + 64 * q;
-                if (q < PSH_NSTAGE - 1 || m < nq) {
-                    const f32x4 v = st.v[q] * scale;
-                    const f32x4 v2 = v * v;
-                    *reinterpret_cast<f16x4*>(a1 + mx_half(4 * m)) = __builtin_convertvector(v, f16x4);
-                    *reinterpret_cast<f16x4*>(a2 + mx_half(4 * m)) = __builtin_convertvector(v2, f16x4);
-                }
-            }
-        }
+        mx_convert(st, a1, a2, scale, nfloat, lane);
         wave_lds_fence();
 #ifdef PSH_TUNING
         // PSH_DBG bit 4: the launch's SKELETON -- sample, both barriers, level, ranking, and ONE unit per wave (the one
         // requested before the level is known) instead of the block's share of the ensemble (tools/fused_skeleton.py;
         // results are invalid: the ranking sees too few candidates and says RETRY)
-        const unsigned un = (a.dbg & 16) ? u_hi : grab();
+        const unsigned un = (a.dbg & 16) ? uq.hi : uq.grab(lane);
 #else
-        const unsigned un = grab();
+        const unsigned un = uq.grab(lane);
 #endif
-        if (un < u_hi) load_unit(st, un);
+        if (un < uq.hi) load_unit<ALIGNED>(st, a, unit_decode(a, un), nfloat, lane);
 
         const int m = lane & 31, hk = lane >> 5;
         f16x8 fa[4];
@@ -463,38 +421,13 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_fused_kernel(ScanArgs a
         for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
 #pragma unroll
         for (int s = 0; s < 4; ++s) fa[s] = *reinterpret_cast<const f16x8*>(a2 + mx_half(32 * m + 16 * s + 8 * hk));
-#pragma unroll
-        for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[s], bo[s], acc, 0, 0, 0);
+        acc = mx_mac4(fa, bo, acc);
 #pragma unroll
         for (int s = 0; s < 4; ++s) fa[s] = *reinterpret_cast<const f16x8*>(a1 + mx_half(32 * m + 16 * s + 8 * hk));
-#pragma unroll
-        for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[s], bx[s], acc, 0, 0, 0);
-        bool keep = false;                                 // NaN-safe: !(t^ > thr)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) keep = keep || !(acc[r] > thr2);
-        if (__any(keep)) {
-            unsigned hm = 0u;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) hm |= !(acc[r] > thr2) ? (1u << r) : 0u;
-#pragma unroll 1
-            for (int r = 0; r < 16; ++r) {
-                const int p = 32 * ((r & 3) + 8 * (r >> 2) + 4 * hk) + m;      // C layout: row -> window
-                bool hit = (((hm >> r) & 1u) != 0u) && (seg_start + p < a.Tp);
-                if (!__ballot(hit)) continue;
-                float v = 0.0f;
-                if (hit) { if constexpr (WT > 0) v = exact_one<(WT > 0 ? WT : 20)>(tile, p, x); else v = exact_one_rt(tile, p, x, W); }
-                hit = hit && (v < tau2);
-                const unsigned long long mask = __ballot(hit);
-                if (!mask) continue;
-                int base = 0;
-                if (lane == 0) base = atomicAdd(&ctl[C_FRONT], __popcll(mask));
-                base = __builtin_amdgcn_readfirstlane(base);
-                if (hit) {
-                    const int slot = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-                    if (slot < PSH_FUSED_FRONT) fl[slot] = u32x4{__float_as_uint(v), (unsigned)r_global, (unsigned)(seg_start + p), 0u};
-                }
-            }
-        }
+        acc = mx_mac4(fa, bx, acc);
+        // (a front list that overflows shows in its cursor: phase D says PSH_STATUS_RETRY)
+        if (mx_any_keep(acc, thr2))
+            mx_admit<WT>(acc, thr2, tau2, tile, x, W, seg_start, a.Tp, r_global, 0u, fl, PSH_FUSED_FRONT, &ctl[C_FRONT], lane, [](float, int) {});
         wave_lds_fence();  // all lanes done with the tile before it is overwritten
         u = un;
     }
@@ -521,7 +454,7 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_fused_kernel(ScanArgs a
         // second barrier: sweep the counts of all blocks
         const int nblk = (int)gridDim.x;
         unsigned cv[PSH_FUSED_MAX_BLOCKS / 64];
-        const __amdgpu_buffer_rsrc_t rblk = g_rsrc(hdr->blk, sizeof(hdr->blk) + sizeof(hdr->blk2));   // blk, then blk2
+        const __amdgpu_buffer_rsrc_t rblk = buffer_rsrc(hdr->blk, sizeof(hdr->blk) + sizeof(hdr->blk2));   // blk, then blk2
         for (;;) {
             bool ok = true;
             u64 xg[PSH_FUSED_MAX_BLOCKS / 64];
@@ -594,7 +527,7 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_fused_kernel(ScanArgs a
         // the live candidates, compacted: candidate c = tid + 1024 i sits in slot c - offs[b] of the block b that owns
         // it (binary search over the 257 prefix sums in LDS); all loads of a thread in flight together
         const int ns = (ntotal + PSH_SCAN_THREADS - 1) / PSH_SCAN_THREADS;
-        const __amdgpu_buffer_rsrc_t rc = g_rsrc(hdr->cand, sizeof(hdr->cand));
+        const __amdgpu_buffer_rsrc_t rc = buffer_rsrc(hdr->cand, sizeof(hdr->cand));
         u32x4v ent[NE];
 #pragma unroll
         for (int i = 0; i < NE; ++i) {
@@ -734,7 +667,7 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_fused_kernel(ScanArgs a
             unsigned* cnt = &hdr->pad[4 + shard];
             const unsigned old = __hip_atomic_fetch_add((gu32*)cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (old + 1u == in_shard) {
-                g_store32(cnt, 0u);
+                store_sc1(cnt, 0u);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 store32_system(f.done + shard, f.done_val);
             }

@@ -20,12 +20,10 @@
 // The launches around it are the separate launches' (psh_capi.hip): bootstrap -> threshold_kernel -> scan -> select_kernel.
 // Results are the exact top-k: what is ranked is always the sequential fp32 chain (include/psh.h).
 #include <type_traits>
-#include "psh_device.h"
+#include "psh_segment.h"
 
 namespace psh {
 
-typedef unsigned long long u64;
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 
 #define PSH_LQ_THREADS 512
 #define PSH_LQ_ROW 40                 // halves a row of 32 samples takes (8 of padding: ds_read_b128 of 16 rows on 16 bank quads)
@@ -39,11 +37,6 @@ typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 //  psh_stream.hip, lays its tables out the same way)
 __host__ __device__ inline size_t lq_wave_bytes(int nks) {
     return (size_t)PSH_LQ_SFLOATS * 4 + (size_t)PSH_LQ_QCAP * 8 + (size_t)lq_rows(nks) * PSH_LQ_ROW * 2;
-}
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float lq_dpp_add(float inc) {
-    return inc + __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(inc), CTRL, ROW_MASK, 0xf, true));
 }
 
 // MODE: PSH_MODE_BOOT / PSH_MODE_FILTER.  NKS: K-steps compiled in.
@@ -70,21 +63,14 @@ __global__ __launch_bounds__(PSH_LQ_THREADS) void scan_lq_kernel(ScanArgs a) {
     _Float16* a1 = reinterpret_cast<_Float16*>(sq_tq + PSH_LQ_QCAP);          // rows of {y^ [32], pad [8]}
 
     const int nfloat = PSH_SEG + W - 1;
-    const unsigned n_rs = (unsigned)a.n_rows * (unsigned)a.nseg;
-    const unsigned u_lo = (unsigned)(((u64)n_rs * blockIdx.x) / gridDim.x);
-    const unsigned u_hi = (unsigned)(((u64)n_rs * (blockIdx.x + 1u)) / gridDim.x);
-    auto decode = [&](unsigned uu, unsigned& ri, unsigned& sg) {
-        ri = fast_div(uu, a.magic_nseg, (unsigned)a.nseg);
-        sg = uu - ri * (unsigned)a.nseg;
-    };
+    const UnitQueue uq = unit_queue((unsigned)a.n_rows * (unsigned)a.nseg, &ctl[1]);
     const int lane16 = lane * 16;
     // (two units in flight per wave -- a second Stage, the loop body twice -- moved the kernel's floor at W = 64 from 1.33 to 1.02 ms
     //  and nothing at W >= 126, where the floor is the per-segment work, not the loaded latency: not kept)
     Stage st;
     auto stage_row = [&](Stage& st, int64_t row, int seg_start) {
         const int64_t bytes = a.T * 4;
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.dataset + row * a.T), 0,
-                                                                             (int)(bytes > 0x7ffffffc ? 0x7ffffffc : bytes), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs = buffer_rsrc(a.dataset + row * a.T, (unsigned)(bytes > 0x7ffffffc ? 0x7ffffffc : bytes));
         const int nq4 = (nfloat + 3) >> 2;
 #pragma unroll
         for (int q = 0; q < PSH_NSTAGE; ++q)
@@ -94,12 +80,11 @@ __global__ __launch_bounds__(PSH_LQ_THREADS) void scan_lq_kernel(ScanArgs a) {
             }
     };
     auto load_unit = [&](Stage& sx, unsigned uu) {
-        unsigned ri, sg;
-        decode(uu, ri, sg);
-        stage_row(sx, a.row0 + (int64_t)ri * a.row_stride, (int)sg * PSH_SEG);
+        const Unit c = unit_decode(a, uu);
+        stage_row(sx, c.row(a), c.seg_start());
     };
-    unsigned u = u_lo + (unsigned)wave;
-    if (u < u_hi) load_unit(st, u);
+    unsigned u = uq.lo + (unsigned)wave;
+    if (u < uq.hi) load_unit(st, u);
 
     // ---- the chunk's scale and per-query constants.  One f16 scale 2^sexp for the chunk: max|x_q| 2^sexp < 8 for every query,
     //      and (FILTER) tau_q 4^sexp <= 4096 -- the fused launch's rule (psh_fused.hip, derive_levels).  A query whose level or
@@ -182,11 +167,6 @@ __global__ __launch_bounds__(PSH_LQ_THREADS) void scan_lq_kernel(ScanArgs a) {
         for (int i = lane; i < lq_rows(NKS) * PSH_LQ_ROW / 2; i += 64) z[i] = 0u;
     }
     wave_lds_fence();
-    auto grab = [&]() -> unsigned {
-        int v = 0;
-        if (lane == 0) v = atomicAdd(&ctl[1], 1);
-        return u_lo + (unsigned)__builtin_amdgcn_readfirstlane(v);
-    };
 
     // ---- deferred survivors (stream_scan_long_kernel's scheme): verified a lane a window, straight from memory
     int qn = 0;
@@ -235,11 +215,10 @@ __global__ __launch_bounds__(PSH_LQ_THREADS) void scan_lq_kernel(ScanArgs a) {
     const _Float16* pb0 = tab + ((size_t)(m & 7) * CP + (hk - (m >> 3) + 3)) * 8;       // copy n & 7, chunk hk - (n >> 3) + 3 (+ 2 s a K-step)
     const float* ps_lo = sp + m + 128 * hk;
     const float* ps_hi = ps_lo + W;
-    while (u < u_hi) {
-        unsigned ri, sg;
-        decode(u, ri, sg);
-        const int64_t row = a.row0 + (int64_t)ri * a.row_stride;
-        const int seg_start = (int)sg * PSH_SEG;
+    while (u < uq.hi) {
+        const Unit c = unit_decode(a, u);
+        const int64_t row = c.row(a);
+        const int seg_start = c.seg_start();
         bool clean;                                                           // the segment holds no NaN / inf and nothing the f16 rows overflow on
         {
             // f16 rows and the fp32 prefix sums of the squares (psh_stream.hip, stream_scan_long_kernel: the bound is there)
@@ -256,17 +235,17 @@ __global__ __launch_bounds__(PSH_LQ_THREADS) void scan_lq_kernel(ScanArgs a) {
                 inc[q] = d3[q];
             }
 #pragma unroll
-            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = lq_dpp_add<0x111, 0xf>(inc[q]);
+            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_add<0x111, 0xf>(inc[q]);
 #pragma unroll
-            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = lq_dpp_add<0x112, 0xf>(inc[q]);
+            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_add<0x112, 0xf>(inc[q]);
 #pragma unroll
-            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = lq_dpp_add<0x114, 0xf>(inc[q]);
+            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_add<0x114, 0xf>(inc[q]);
 #pragma unroll
-            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = lq_dpp_add<0x118, 0xf>(inc[q]);
+            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_add<0x118, 0xf>(inc[q]);
 #pragma unroll
-            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = lq_dpp_add<0x142, 0xa>(inc[q]);
+            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_add<0x142, 0xa>(inc[q]);
 #pragma unroll
-            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = lq_dpp_add<0x143, 0xc>(inc[q]);
+            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_add<0x143, 0xc>(inc[q]);
             float carry = 0.0f;
 #pragma unroll
             for (int q = 0; q < PSH_NSTAGE; ++q) {
@@ -282,8 +261,8 @@ __global__ __launch_bounds__(PSH_LQ_THREADS) void scan_lq_kernel(ScanArgs a) {
             clean = __builtin_amdgcn_readfirstlane(carry < 4.0e9f ? 1 : 0) != 0;
         }
         wave_lds_fence();
-        const unsigned un = grab();
-        if (un < u_hi) load_unit(st, un);
+        const unsigned un = uq.grab(lane);
+        if (un < uq.hi) load_unit(st, un);
         // the tile's C operand from the prefix sums: FILTER a LOWER bound of the energies (E^ - gamma S), BOOT an UPPER one
         f32x16 ce;
 #pragma unroll
@@ -299,7 +278,7 @@ __global__ __launch_bounds__(PSH_LQ_THREADS) void scan_lq_kernel(ScanArgs a) {
             // W squared differences) -- a quarter of all tiles went through the survivors' code for windows that do not exist.
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                if (32 * ((r & 3) + 8 * (r >> 2) + 4 * hk) + m >= nvalid) ce[r] = __uint_as_float(PSH_INF_BITS);
+                if (mx_window(r, lane) >= nvalid) ce[r] = __uint_as_float(PSH_INF_BITS);
         }
         // BOOT: the minimum of an upper bound of acc per (unit, query)
         auto boot_finish = [&](const f32x16& c, const int ql) __attribute__((always_inline)) {
@@ -310,7 +289,7 @@ __global__ __launch_bounds__(PSH_LQ_THREADS) void scan_lq_kernel(ScanArgs a) {
             } else {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int p = 32 * ((r & 3) + 8 * (r >> 2) + 4 * hk) + m;
+                    const int p = mx_window(r, lane);
                     mn = p < nvalid ? fminf(mn, c[r]) : mn;
                 }
             }
@@ -366,7 +345,7 @@ __global__ __launch_bounds__(PSH_LQ_THREADS) void scan_lq_kernel(ScanArgs a) {
             if (nvalid < PSH_SEG) {                                           // a row's last segment: windows that do not exist
 #pragma unroll 1
                 for (int r = 0; r < 16; ++r)
-                    if (32 * ((r & 3) + 8 * (r >> 2) + 4 * hk) + m >= nvalid) hm &= ~(1u << r);
+                    if (mx_window(r, lane) >= nvalid) hm &= ~(1u << r);
             }
 #ifdef PSH_TUNING
             if (a.dbg & 4) hm = 0u;                                           // ablation: no survivor handling (results invalid)
@@ -385,7 +364,7 @@ __global__ __launch_bounds__(PSH_LQ_THREADS) void scan_lq_kernel(ScanArgs a) {
                     for (; h; h &= h - 1u, ++slot) {
                         const int r = __builtin_ctz(h);
                         sq_row[slot] = (unsigned)row;
-                        sq_tq[slot] = (unsigned)(seg_start + 32 * ((r & 3) + 8 * (r >> 2) + 4 * hk) + m) | ((unsigned)ql << 27);
+                        sq_tq[slot] = (unsigned)(seg_start + mx_window(r, lane)) | ((unsigned)ql << 27);
                     }
                 }
                 qn += n;

@@ -1,6 +1,7 @@
 // psh_scan.hip -- gfx950 (MI355X, CDNA4) kernels of the k-nearest-path scan: the Identity scans (scan_kernel,
 // scan_mx_kernel, scan_mq_kernel, scan_mq8_kernel, mq_prep_kernel, boot_mq_kernel) and their launchers.  The embedded / one-window-row scans are in
-// psh_embed.hip, thresholding / selection / merge / gather in psh_select.hip, shared device code in psh_device.h.
+// psh_embed.hip, thresholding / selection / merge / gather in psh_select.hip, shared device code in psh_device.h (helpers,
+// window arithmetic, candidate append) and psh_segment.h (staging, a block's unit queue, the one-query matrix-core segment test).
 //
 // What is computed (reference RudyMorel/shadowing, shadowing/path_shadowing/):
 //   path_embedding.py:129-139  Identity embedding == the window y[r, t:t+W] itself
@@ -35,7 +36,7 @@
 //     part; 5e4 of them were 5x the whole scan).  A one-block radix select then picks the
 //     k best and orders them by (d, r, t).
 //   * the embedded scan (embed_scan_kernel) runs the same pipeline behind a linear embedding.
-#include "psh_device.h"
+#include "psh_segment.h"
 
 namespace psh {
 
@@ -56,11 +57,7 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_kernel(ScanArgs a) {
     int* lcount = reinterpret_cast<int*>(smem + (size_t)(PSH_SCAN_THREADS / 64) * a.tile_floats);
     u32x4* pend = reinterpret_cast<u32x4*>(lcount + ((a.B + 3) & ~3) + 4) + (size_t)wave_in_block * PSH_PEND;
     int npend = 0;                                       // wave-uniform
-    // lcount[B .. ]: the block's work cursor.  Waves of one SIMD are served oldest first,
-    // so with a static split the young waves of every SIMD finish up to 2x later than the
-    // old ones and the tail of the launch runs at a fraction of the occupancy (measured:
-    // waves end between 69 and 149 us).  All 16 waves of the block therefore pull
-    // segments from one LDS counter; the block's own share of the units is static.
+    // lcount[B .. ]: the block's work cursor (UnitQueue, psh_segment.h)
     int* next_unit = lcount + ((a.B + 3) & ~3);
     if (threadIdx.x == 0) { next_unit[0] = 0; next_unit[1] = 0; }
     if (MODE == PSH_MODE_FILTER)
@@ -71,42 +68,23 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_kernel(ScanArgs a) {
     const int W = WT > 0 ? WT : a.W;
     const int nfloat = PSH_SEG + W - 1;
     const unsigned n_rs = (unsigned)a.n_rows * (unsigned)a.nseg;      // (row, segment) units
-    const unsigned n_units = n_rs * (unsigned)a.n_qgroups;             // host guarantees < 2^31
-    const unsigned u_lo = (unsigned)(((unsigned long long)n_units * blockIdx.x) / gridDim.x);
-    const unsigned u_hi = (unsigned)(((unsigned long long)n_units * (blockIdx.x + 1)) / gridDim.x);
+    const UnitQueue uq = unit_queue(n_rs * (unsigned)a.n_qgroups, next_unit);
     const unsigned gw = blockIdx.x * (PSH_SCAN_THREADS / 64) + (unsigned)wave_in_block;
     const const_f32p xq = (const_f32p)a.queries;
     // per-query state through the scalar cache: no VGPR destination, no vmcnt
     typedef const __attribute__((address_space(4))) QueryState* const_qsp;
     const const_qsp qstate_k = (const_qsp)a.qstate;
 
-    auto grab = [&]() -> unsigned {   // next unit of this block (wave-uniform), >= u_hi when exhausted
-        int v = 0;
-        if (lane == 0) v = atomicAdd(next_unit, 1);
-        return u_lo + (unsigned)__builtin_amdgcn_readfirstlane(v);
-    };
-
     if (a.dbg_times && lane == 0) a.dbg_times[2 * gw] = wall_clock64();
     Stage st;
-    unsigned u = grab();
-    // unit -> (query group, row index, segment)
-    auto decode = [&](unsigned uu, unsigned& rs, unsigned& ri, unsigned& sg, unsigned& qgi) {
-        qgi = fast_div(uu, a.magic_nrs, n_rs);
-        rs = uu - qgi * n_rs;
-        ri = fast_div(rs, a.magic_nseg, (unsigned)a.nseg);
-        sg = rs - ri * (unsigned)a.nseg;
-    };
-    unsigned rs, ri, sg, qgi;
-    if (u < u_hi) {
-        decode(u, rs, ri, sg, qgi);
-        const int64_t row = a.row0 + (int64_t)ri * a.row_stride;
-        stage_load<ALIGNED>(st, a.dataset + row * a.T, a.T, (int)sg * PSH_SEG, nfloat, lane);
-    }
-    while (u < u_hi) {
-        decode(u, rs, ri, sg, qgi);
-        const int qg = (int)qgi;
-        const int64_t row = a.row0 + (int64_t)ri * a.row_stride;
-        const int seg_start = (int)sg * PSH_SEG;
+    unsigned u = uq.grab(lane);
+    if (u < uq.hi) load_unit<ALIGNED>(st, a, unit_decode(a, u, n_rs), nfloat, lane);
+    while (u < uq.hi) {
+        const Unit c = unit_decode(a, u, n_rs);
+        const unsigned rs = c.rs;
+        const int qg = (int)c.qg;
+        const int64_t row = c.row(a);
+        const int seg_start = c.seg_start();
 
         stage_store(st, tile, nfloat, lane);
         if (MODE == PSH_MODE_BOOT && a.blockmax) {
@@ -122,17 +100,11 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_kernel(ScanArgs a) {
             pend_flush(pend, npend, lcount, a, lane);
             npend = 0;
         }
-        const unsigned un = grab();
-        {   // prefetch the next unit of this wave while this one is computed.  (Spreading
-            // these five loads over the arithmetic through a hook was tried: +6 % time --
-            // the extra live ranges cost a spill at the 128-VGPR cap.)
-            if (un < u_hi) {
-                unsigned rsn, rin, sgn, qgn;
-                decode(un, rsn, rin, sgn, qgn);
-                const int64_t rown = a.row0 + (int64_t)rin * a.row_stride;
-                stage_load<ALIGNED>(st, a.dataset + rown * a.T, a.T, (int)sgn * PSH_SEG, nfloat, lane);
-            }
-        }
+        const unsigned un = uq.grab(lane);
+        // prefetch the next unit of this wave while this one is computed.  (Spreading
+        // these five loads over the arithmetic through a hook was tried: +6 % time --
+        // the extra live ranges cost a spill at the 128-VGPR cap.)
+        if (un < uq.hi) load_unit<ALIGNED>(st, a, unit_decode(a, un, n_rs), nfloat, lane);
 
         const int t_lane = seg_start + PSH_L * lane;           // first window of this lane
         int nvalid = a.Tp - t_lane;                             // admissible windows of this lane
@@ -302,7 +274,8 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_kernel(ScanArgs a) {
 // rightly rejected when its t^ comes out +inf, and is kept for the exact recheck when it
 // comes out NaN (inf * 0 from the zero part of the band, inf - inf): both are correct.
 // ----------------------------------------------------------------------------------
-// (f16x8 / f16x4 / f32x16, PSH_MX_SLOTS / NHALF / PEND and mx_half(): psh_device.h -- shared with psh_fused.hip)
+// (f16x8 / f16x4 / f32x16, PSH_MX_SLOTS / NHALF / PEND, mx_half() and the pieces of the test itself: psh_segment.h -- shared
+//  with psh_fused.hip and psh_stream.hip)
 
 template <int WT, bool ALIGNED>
 __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_mx_kernel(ScanArgs a) {
@@ -323,17 +296,12 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_mx_kernel(ScanArgs a) {
     const int gw_dbg = (int)blockIdx.x * NW + wave_in_block;
     if (a.dbg_times && lane == 0) a.dbg_times[2 * gw_dbg] = wall_clock64();   // tuning aid (tools/wave_times.py)
     if (threadIdx.x == 0) { *next_unit = 0; lcount[0] = 0; lcount[1] = 0; }
-    {   // the tail slots no segment ever writes must hold finite values (0 * NaN poisons a row)
-        unsigned* z = reinterpret_cast<unsigned*>(ah);
-        for (int i = lane; i < PSH_MX_NHALF; i += 64) z[i] = 0u;          // 2 arrays x NHALF halves = NHALF dwords
-    }
+    mx_zero(ah, lane);
     __syncthreads();
 
     const int W = WT > 0 ? WT : a.W;
     const int nfloat = PSH_SEG + W - 1;
-    const unsigned n_rs = (unsigned)a.n_rows * (unsigned)a.nseg;
-    const unsigned u_lo = (unsigned)(((unsigned long long)n_rs * blockIdx.x) / gridDim.x);
-    const unsigned u_hi = (unsigned)(((unsigned long long)n_rs * (blockIdx.x + 1)) / gridDim.x);
+    const UnitQueue uq = unit_queue((unsigned)a.n_rows * (unsigned)a.nseg, next_unit);
     const const_f32p x = (const_f32p)a.queries;
     typedef const __attribute__((address_space(4))) QueryState* const_qsp;
     const const_qsp qs = (const_qsp)a.qstate;
@@ -345,31 +313,9 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_mx_kernel(ScanArgs a) {
     // (if the threshold kernel could not arm the filter -- absurd magnitudes -- scale is 0 and
     // thr +inf: nothing is rejected, every window goes through exact_one: slow, still exact)
 
-    // B fragments: lane (n = lane & 31, hk = lane >> 5) holds k = 16 s + 8 hk + i, i < 8
     f16x8 bx[4], bo[4];
-    {
-        const int n = lane & 31, hk = lane >> 5;
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int j = 16 * s + 8 * hk + i - n;
-                const bool in = j >= 0 && j < W;
-                const float xv = x[in ? j : 0];
-                bx[s][i] = (_Float16)(in ? -2.0f * (xv * scale) : 0.0f);
-                bo[s][i] = (_Float16)(in ? 1.0f : 0.0f);
-            }
-    }
-
-    auto grab = [&]() -> unsigned {
-        int v = 0;
-        if (lane == 0) v = atomicAdd(next_unit, 1);
-        return u_lo + (unsigned)__builtin_amdgcn_readfirstlane(v);
-    };
-    auto decode = [&](unsigned uu, unsigned& ri, unsigned& sg) {
-        ri = fast_div(uu, a.magic_nseg, (unsigned)a.nseg);
-        sg = uu - ri * (unsigned)a.nseg;
-    };
+    mx_band_ones(bo, W, lane);
+    mx_band_query(bx, x, scale, W, lane);
 
     const float xn = qs[0].xn;
     // candidate append of this kernel: one query, its norm in an SGPR -- stores only, so that
@@ -393,36 +339,18 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_mx_kernel(ScanArgs a) {
         }
         npend = 0;
     };
-    auto load_unit = [&](Stage& sx, unsigned uu) {
-        unsigned ri, sg;
-        decode(uu, ri, sg);
-        stage_load<ALIGNED>(sx, a.dataset + (a.row0 + (int64_t)ri * a.row_stride) * a.T, a.T, (int)sg * PSH_SEG, nfloat, lane);
-    };
     // one segment: `cur` holds its values; returns the unit whose load now occupies `cur`
     auto process = [&](Stage& cur, unsigned ucur) -> unsigned {
-        unsigned ri, sg;
-        decode(ucur, ri, sg);
-        const int64_t row = a.row0 + (int64_t)ri * a.row_stride;
-        const int seg_start = (int)sg * PSH_SEG;
+        const Unit c = unit_decode(a, ucur);
+        const int64_t row = c.row(a);
+        const int seg_start = c.seg_start();
 
         stage_store(cur, tile, nfloat, lane);
-        {   // the f16 copies: y^ and (y~^2)^, 4 values = one 8-byte store per array and chunk
-            const int nq = (nfloat + 3) >> 2;
-#pragma unroll
-            for (int q = 0; q < PSH_NSTAGE; ++q) {
-                const int m = lane + 64 * q;
-                if (q < PSH_NSTAGE - 1 || m < nq) {
-                    const f32x4 v = cur.v[q] * scale;
-                    const f32x4 v2 = v * v;
-                    *reinterpret_cast<f16x4*>(a1 + mx_half(4 * m)) = __builtin_convertvector(v, f16x4);
-                    *reinterpret_cast<f16x4*>(a2 + mx_half(4 * m)) = __builtin_convertvector(v2, f16x4);
-                }
-            }
-        }
+        mx_convert(cur, a1, a2, scale, nfloat, lane);
         wave_lds_fence();
         if (npend > 0) flush();   // last segment's admissions, ahead of the prefetch
-        const unsigned un = grab();
-        if (un < u_hi) load_unit(cur, un);
+        const unsigned un = uq.grab(lane);
+        if (un < uq.hi) load_unit<ALIGNED>(cur, a, unit_decode(a, un), nfloat, lane);
 
         const int r_global = (int)(row + a.r_offset);
         auto push = [&](bool hit, float v, int t) {      // wave-uniform control flow
@@ -442,32 +370,15 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_mx_kernel(ScanArgs a) {
         };
 
         {
-            const int m = lane & 31, hk = lane >> 5;
-            f16x8 fa[4];                                   // four A fragments per LDS round trip
-            f32x16 acc;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) fa[s] = *reinterpret_cast<const f16x8*>(a2 + mx_half(32 * m + 16 * s + 8 * hk));
-#pragma unroll
-            for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[s], bo[s], acc, 0, 0, 0);
-#pragma unroll
-            for (int s = 0; s < 4; ++s) fa[s] = *reinterpret_cast<const f16x8*>(a1 + mx_half(32 * m + 16 * s + 8 * hk));
-#pragma unroll
-            for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[s], bx[s], acc, 0, 0, 0);
-            bool keep = false;                             // NaN-safe: !(t^ > thr)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) keep = keep || !(acc[r] > thr);
-            if (__any(keep)) {                             // about one segment in four
-                unsigned hm = 0u, hm2 = 0u;                // bit r: window of accumulator r survives tau / tau2
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    hm |= !(acc[r] > thr) ? (1u << r) : 0u;
-                    hm2 |= !(acc[r] > thr2) ? (1u << r) : 0u;
-                }
+            f16x8 fa[4];
+            f32x16 acc = mx_energies(fa, a2, bo, lane);
+            mx_load_a(fa, a1, lane);
+            acc = mx_mac4(fa, bx, acc);
+            if (mx_any_keep(acc, thr)) {
+                const unsigned hm = mx_keep_mask(acc, thr), hm2 = mx_keep_mask(acc, thr2);   // survives tau / tau2
 #pragma unroll 1
                 for (int r = 0; r < 16; ++r) {
-                    const int p = 32 * ((r & 3) + 8 * (r >> 2) + 4 * hk) + m;      // C layout: row -> window
+                    const int p = mx_window(r, lane);
                     const bool hit = (((hm >> r) & 1u) != 0u) && (seg_start + p < a.Tp);
                     if (!__ballot(hit)) continue;
                     // the exact chain only where the window may still be below tau2; the others are admitted
@@ -475,7 +386,7 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_mx_kernel(ScanArgs a) {
                     const bool may2 = hit && (((hm2 >> r) & 1u) != 0u);
                     float v = __uint_as_float(PSH_UNVERIFIED_BITS);
                     if (__ballot(may2)) {
-                        if (may2) { if constexpr (WT > 0) v = exact_one<(WT > 0 ? WT : 20)>(tile, p, x); else v = exact_one_rt(tile, p, x, W); }
+                        if (may2) v = mx_exact<WT>(tile, p, x, W);
                     }
                     push(hit && (!may2 || v < tau), v, seg_start + p);
                 }
@@ -488,9 +399,9 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_mx_kernel(ScanArgs a) {
     // one segment in flight per wave besides the one being processed.  (Two in flight --
     // a second Stage, consumed one iteration later -- was measured: 89.6 us against 82.9.)
     Stage st;
-    unsigned u = grab();
-    if (u < u_hi) load_unit(st, u);
-    while (u < u_hi) u = process(st, u);
+    unsigned u = uq.grab(lane);
+    if (u < uq.hi) load_unit<ALIGNED>(st, a, unit_decode(a, u), nfloat, lane);
+    while (u < uq.hi) u = process(st, u);
     if (a.dbg_times && lane == 0) a.dbg_times[2 * gw_dbg + 1] = wall_clock64();
     if (npend > 0) flush();
     __syncthreads();
@@ -586,9 +497,7 @@ __global__ __launch_bounds__(PSH_MQ_THREADS) void scan_mq_kernel(ScanArgs a) {
     __syncthreads();
 
     const int nfloat = PSH_SEG + W - 1;
-    const unsigned n_rs = (unsigned)a.n_rows * (unsigned)a.nseg;
-    const unsigned u_lo = (unsigned)(((unsigned long long)n_rs * blockIdx.x) / gridDim.x);
-    const unsigned u_hi = (unsigned)(((unsigned long long)n_rs * (blockIdx.x + 1)) / gridDim.x);
+    const UnitQueue uq = unit_queue((unsigned)a.n_rows * (unsigned)a.nseg, next_unit);
     typedef const __attribute__((address_space(4))) QueryState* const_qsp;
     const float scale = ((const_qsp)a.qstate)[0].mx_scale;                // one scale for the whole batch
     const int n = lane & 31, hk = lane >> 5, qsub = n >> 3, shift = n & 7;
@@ -602,29 +511,18 @@ __global__ __launch_bounds__(PSH_MQ_THREADS) void scan_mq_kernel(ScanArgs a) {
             bo[s][i] = (_Float16)((j >= 0 && j < W) ? 1.0f : 0.0f);
         }
 
-    auto grab = [&]() -> unsigned {
-        int v = 0;
-        if (lane == 0) v = atomicAdd(next_unit, 1);
-        return u_lo + (unsigned)__builtin_amdgcn_readfirstlane(v);
-    };
-    auto load_unit = [&](Stage& sx, unsigned uu) {
-        const unsigned ri = fast_div(uu, a.magic_nseg, (unsigned)a.nseg);
-        const unsigned sg = uu - ri * (unsigned)a.nseg;
-        stage_load<ALIGNED>(sx, a.dataset + (a.row0 + (int64_t)ri * a.row_stride) * a.T, a.T, (int)sg * PSH_SEG, nfloat, lane);
-    };
 
 #ifdef PSH_TUNING
     const int dbg = __builtin_amdgcn_readfirstlane(a.dbg);
     if ((dbg & 1) && wave_in_block >= 4) __builtin_amdgcn_s_setprio(1);       // the second wave of every SIMD ahead of the first
 #endif
     Stage st;
-    unsigned u = grab();
-    if (u < u_hi) load_unit(st, u);
-    while (u < u_hi) {
-        const unsigned ri = fast_div(u, a.magic_nseg, (unsigned)a.nseg);
-        const unsigned sg = u - ri * (unsigned)a.nseg;
-        const int64_t row = a.row0 + (int64_t)ri * a.row_stride;
-        const int seg_start = (int)sg * PSH_SEG;
+    unsigned u = uq.grab(lane);
+    if (u < uq.hi) load_unit<ALIGNED>(st, a, unit_decode(a, u), nfloat, lane);
+    while (u < uq.hi) {
+        const Unit c = unit_decode(a, u);
+        const int64_t row = c.row(a);
+        const int seg_start = c.seg_start();
         const int r_global = (int)(row + a.r_offset);
 
         float lmax = 0.0f, nanq = 0.0f;
@@ -673,8 +571,8 @@ __global__ __launch_bounds__(PSH_MQ_THREADS) void scan_mq_kernel(ScanArgs a) {
         // then is the next unit requested into the staging registers
         wave_lds_fence();
         stage_store(st, tile, nfloat, lane);
-        const unsigned un = grab();
-        if (un < u_hi) load_unit(st, un);
+        const unsigned un = uq.grab(lane);
+        if (un < uq.hi) load_unit<ALIGNED>(st, a, unit_decode(a, un), nfloat, lane);
 
         // the exact chain for the queued survivors, one per lane
         auto drain = [&]() {
@@ -913,6 +811,8 @@ __global__ __launch_bounds__(PSH_MQ_THREADS) void scan_mq8_kernel(ScanArgs a) {
     __syncthreads();
 
     const int nfloat = PSH_SEG + W - 1;
+    // (this kernel keeps its own copy of the unit queue of psh_segment.h: with the shared one its scan measured 2.5 % slower
+    //  -- 2.43 against 2.37 ms at B = 512 -- although the instruction sequences differ by a handful of scalar moves)
     const unsigned n_rs = (unsigned)a.n_rows * (unsigned)a.nseg;
     const unsigned u_lo = (unsigned)(((unsigned long long)n_rs * blockIdx.x) / gridDim.x);
     const unsigned u_hi = (unsigned)(((unsigned long long)n_rs * (blockIdx.x + 1)) / gridDim.x);
@@ -929,6 +829,7 @@ __global__ __launch_bounds__(PSH_MQ_THREADS) void scan_mq8_kernel(ScanArgs a) {
             const int j = 16 * s + 8 * hk + i - shift;
             bo[s][i] = (_Float16)((j >= 0 && j < W) ? 1.0f : 0.0f);
         }
+
 
     auto grab = [&]() -> unsigned {
         int v = 0;
@@ -1318,9 +1219,7 @@ __global__ __launch_bounds__(PSH_MQ_THREADS) void boot_mq_kernel(ScanArgs a) {
     __syncthreads();
 
     const int nfloat = PSH_SEG + W - 1;
-    const unsigned n_rs = (unsigned)a.n_rows * (unsigned)a.nseg;
-    const unsigned u_lo = (unsigned)(((unsigned long long)n_rs * blockIdx.x) / gridDim.x);
-    const unsigned u_hi = (unsigned)(((unsigned long long)n_rs * (blockIdx.x + 1)) / gridDim.x);
+    const UnitQueue uq = unit_queue((unsigned)a.n_rows * (unsigned)a.nseg, next_unit);
     const int n = lane & 31, hk = lane >> 5, qsub = n >> 3, shift = n & 7;
     const const_f32p xk = (const_f32p)a.queries;
     // acc~ <= (nx~ (1 + 3a) + t^ + b) / (1 - 2a), a = 2^-9, b = 2^-18; constants rounded up, fp32 slack included
@@ -1341,25 +1240,14 @@ __global__ __launch_bounds__(PSH_MQ_THREADS) void boot_mq_kernel(ScanArgs a) {
             const int j = 16 * s + 8 * hk + i - shift;
             bo[s][i] = (_Float16)((j >= 0 && j < W) ? 1.0f : 0.0f);
         }
-    auto grab = [&]() -> unsigned {
-        int v = 0;
-        if (lane == 0) v = atomicAdd(next_unit, 1);
-        return u_lo + (unsigned)__builtin_amdgcn_readfirstlane(v);
-    };
-    auto load_unit = [&](Stage& sx, unsigned uu) {
-        const unsigned ri = fast_div(uu, a.magic_nseg, (unsigned)a.nseg);
-        const unsigned sg = uu - ri * (unsigned)a.nseg;
-        stage_load<ALIGNED>(sx, a.dataset + (a.row0 + (int64_t)ri * a.row_stride) * a.T, a.T, (int)sg * PSH_SEG, nfloat, lane);
-    };
 
     float wmax = 0.0f;
     Stage st;
-    unsigned u = grab();
-    if (u < u_hi) load_unit(st, u);
-    while (u < u_hi) {
-        const unsigned ri = fast_div(u, a.magic_nseg, (unsigned)a.nseg);
-        const unsigned sg = u - ri * (unsigned)a.nseg;
-        const int seg_start = (int)sg * PSH_SEG;
+    unsigned u = uq.grab(lane);
+    if (u < uq.hi) load_unit<ALIGNED>(st, a, unit_decode(a, u), nfloat, lane);
+    while (u < uq.hi) {
+        const Unit c = unit_decode(a, u);
+        const int seg_start = c.seg_start();
         const bool ragged = seg_start + PSH_SEG > a.Tp;        // some windows of this segment are not admissible
 
         float lmax = 0.0f;
@@ -1381,8 +1269,8 @@ __global__ __launch_bounds__(PSH_MQ_THREADS) void boot_mq_kernel(ScanArgs a) {
         const bool exact = __any(!(lmax * scale <= 128.0f)) || !(scale > 0.0f);   // beyond f16 range: exact chain
         if (exact) stage_store(st, tile, nfloat, lane);
         wave_lds_fence();
-        const unsigned un = grab();
-        if (un < u_hi) load_unit(st, un);
+        const unsigned un = uq.grab(lane);
+        if (un < uq.hi) load_unit<ALIGNED>(st, a, unit_decode(a, un), nfloat, lane);
 
         if (!exact) {
             f32x16 ny[4];

@@ -26,22 +26,11 @@
 // fragments and a threshold test, so a batch of 2 or 3 costs little more than one query, where the batched scan
 // (scan_mq_kernel: 8 waves per CU, sized for hundreds of queries) streams at half rate.  One f16 scale serves all queries of
 // the step: the largest that every query's proof allows (each query bounds it from above by its own max|x| and tau2).
-#include "psh_device.h"
+#include "psh_segment.h"
 
 namespace psh {
 
-typedef unsigned long long u64;
-typedef __attribute__((address_space(1))) u64 gu64;
-typedef __attribute__((address_space(1))) unsigned gu32;
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
-#define PSH_AUX_SC1 16
-
-__device__ __forceinline__ void st_sc1(unsigned* p, unsigned v) {
-    __hip_atomic_store((gu32*)(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t st_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
+// (u64 / gu64 / gu32 / u32x4v, store_sc1, buffer_rsrc, PSH_AUX_SC1: psh_device.h -- shared with psh_fused.hip)
 
 // ------------------------------------------------------------------------------------------------------------------
 // P: the sample and the admission levels
@@ -135,7 +124,7 @@ __device__ __forceinline__ void stream_sample_finish(const ScanArgs& a, const Fu
 #pragma unroll 1
     for (int q = (NWP == 1 ? 0 : wave); q < nq; q += NWP) {
         bool armed = true;
-        const __amdgpu_buffer_rsrc_t rmin = st_rsrc(hdr->minima + (size_t)q * f.units_stride, (unsigned)(4 * n4) * 4u);
+        const __amdgpu_buffer_rsrc_t rmin = buffer_rsrc(hdr->minima + (size_t)q * f.units_stride, (unsigned)(4 * n4) * 4u);
         wave_lds_fence();
         for (int i = lane; i < PSH_STREAM_HIST; i += 64) hist[i] = 0u;
         unsigned kmin = 0xffffffffu, kmax = 0u;
@@ -311,11 +300,6 @@ void stream_sample_kernel(ScanArgs a, FusedArgs f) {
     const bool hinted = f.tau_hint != nullptr;
     const unsigned nbu = hinted ? 0u : (unsigned)f.boot_units;
 
-    auto boot_load = [&](Stage& sx, unsigned uu) {
-        const unsigned ri = fast_div(uu, a.magic_nseg, (unsigned)a.nseg);
-        const unsigned sg = uu - ri * (unsigned)a.nseg;
-        stage_load<ALIGNED>(sx, a.dataset + (f.boot_row0 + (int64_t)ri * f.boot_row_stride) * a.T, a.T, (int)sg * PSH_SEG, nfloat, lane);
-    };
     unsigned u = blockIdx.x * NWP + (unsigned)wave;
     for (int p = lane; p < a.tile_floats; p += 64) tile[p] = 0.0f;           // no slot is ever read uninitialised
     // a header psh_workspace_init never saw: no ticket can be trusted -- block 0 says so, the scan and the ranking return
@@ -325,13 +309,12 @@ void stream_sample_kernel(ScanArgs a, FusedArgs f) {
         return;
     }
     while (u < nbu) {
-        const unsigned ri = fast_div(u, a.magic_nseg, (unsigned)a.nseg);
-        const unsigned sg = u - ri * (unsigned)a.nseg;
-        const int seg_start = (int)sg * PSH_SEG;
+        const Unit c = unit_decode(a, u);
+        const int seg_start = c.seg_start();
         {   // (no register prefetch of the next unit: 20 VGPRs this wave does not have; the other sample waves of the chip
             //  cover the latency)
             Stage st;
-            boot_load(st, u);
+            load_unit<ALIGNED>(st, a, f.boot_row0, f.boot_row_stride, c, nfloat, lane);
             stage_store<false>(st, tile, nfloat, lane);
         }
         wave_lds_fence();
@@ -351,7 +334,7 @@ void stream_sample_kernel(ScanArgs a, FusedArgs f) {
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) m = fminf(m, __shfl_xor(m, off, 64));
             if (!(m == m)) m = __uint_as_float(PSH_INF_BITS);              // NaN data: the segment carries no information
-            if (lane == 0) st_sc1(&hdr->minima[(size_t)q * f.units_stride + u], __float_as_uint(m));   // write-through
+            if (lane == 0) store_sc1(&hdr->minima[(size_t)q * f.units_stride + u], __float_as_uint(m));   // write-through
         }
         wave_lds_fence();
         u = un;
@@ -398,23 +381,12 @@ __device__ __forceinline__ void stream_scan_body(const ScanArgs& a, const FusedA
 
     const int W = WT > 0 ? WT : a.W;
     const int nfloat = PSH_SEG + W - 1;
-    const unsigned n_rs = (unsigned)a.n_rows * (unsigned)a.nseg;
-    const unsigned u_lo = (unsigned)(((u64)n_rs * blockIdx.x) / gridDim.x);
-    const unsigned u_hi = (unsigned)(((u64)n_rs * (blockIdx.x + 1u)) / gridDim.x);
+    const UnitQueue uq = unit_queue((unsigned)a.n_rows * (unsigned)a.nseg, &ctl[S_NEXT]);
 
-    auto decode = [&](unsigned uu, unsigned& ri, unsigned& sg) {
-        ri = fast_div(uu, a.magic_nseg, (unsigned)a.nseg);
-        sg = uu - ri * (unsigned)a.nseg;
-    };
-    auto load_unit = [&](Stage& sx, unsigned uu) {
-        unsigned ri, sg;
-        decode(uu, ri, sg);
-        stage_load<ALIGNED>(sx, a.dataset + (a.row0 + (int64_t)ri * a.row_stride) * a.T, a.T, (int)sg * PSH_SEG, nfloat, lane);
-    };
-    // the first unit of every wave is requested before anything else (static: unit u_lo + wave; the queue starts behind them)
+    // the first unit of every wave is requested before anything else (static: unit lo + wave; the queue starts behind them)
     Stage st;
-    unsigned u = u_lo + (unsigned)wave;
-    if (u < u_hi) load_unit(st, u);
+    unsigned u = uq.lo + (unsigned)wave;
+    if (u < uq.hi) load_unit<ALIGNED>(st, a, unit_decode(a, u), nfloat, lane);
     // what the sample kernel left (an earlier launch on this stream: plain loads): the shifted-query fragments -- one query's in
     // registers; two or three queries' block-shared in LDS, read per use (a second set in registers spills 15 of them inside
     // the loop at the 128-register cap of four waves per SIMD: 142 us for two queries against 107 from LDS; the LDS pipe is
@@ -439,112 +411,45 @@ __device__ __forceinline__ void stream_scan_body(const ScanArgs& a, const FusedA
         xn[q] = __uint_as_float(sc->xn_bits[q]);
     }
     if (tid == 0) { ctl[S_FRONT] = 0; ctl[S_NEXT] = NW; }
-    {   // every slot of the f16 arrays a segment does not write must be finite (0 * NaN poisons a row)
-        unsigned* z = reinterpret_cast<unsigned*>(a1);
-        for (int i = lane; i < PSH_MX_NHALF; i += 64) z[i] = 0u;              // 2 arrays x NHALF halves = NHALF dwords
-    }
-    {   // the band of ones (window energies): arithmetic only
-        const int n = lane & 31, hk = lane >> 5;
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int j = 16 * s + 8 * hk + i - n;
-                bo[s][i] = (_Float16)((j >= 0 && j < W) ? 1.0f : 0.0f);
-            }
-    }
+    mx_zero(a1, lane);
+    mx_band_ones(bo, W, lane);                                                // (window energies: arithmetic only)
     __syncthreads();
     stamp(1);
     if (armed_w == 0u) return;                                                // uniform: the ranking reports PSH_STATUS_RETRY
-    auto grab = [&]() -> unsigned {
-        int v = 0;
-        if (lane == 0) v = atomicAdd(&ctl[S_NEXT], 1);
-        return u_lo + (unsigned)__builtin_amdgcn_readfirstlane(v);
-    };
-    // the survivors of one query's accumulator tile: exact chain from the fp32 tile, admitted below the query's level
+    // the survivors of one query's accumulator tile: exact chain from the fp32 tile, admitted below the query's level; a full
+    // list spills to memory
     auto admit = [&](const f32x16& acc, int q, float thr, float tau, int seg_start, int r_global) {
-        const int m = lane & 31, hk = lane >> 5;
-        const const_f32p x = (const_f32p)a.queries + (size_t)q * W;
-        unsigned hm = 0u;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) hm |= !(acc[r] > thr) ? (1u << r) : 0u;
-#pragma unroll 1
-        for (int r = 0; r < 16; ++r) {
-            const int p = 32 * ((r & 3) + 8 * (r >> 2) + 4 * hk) + m;         // C layout: row -> window
-            bool hit = (((hm >> r) & 1u) != 0u) && (seg_start + p < a.Tp);
-            if (!__ballot(hit)) continue;
-            float v = 0.0f;
-            if (hit) { if constexpr (WT > 0) v = exact_one<(WT > 0 ? WT : 20)>(tile, p, x); else v = exact_one_rt(tile, p, x, W); }
-            hit = hit && (v < tau);
-            const unsigned long long mask = __ballot(hit);
-            if (!mask) continue;
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&ctl[S_FRONT], __popcll(mask));
-            base = __builtin_amdgcn_readfirstlane(base);
-            if (hit) {
-                const int slot = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-                if (slot < NFL) fl[slot] = u32x4{__float_as_uint(v), (unsigned)r_global, (unsigned)(seg_start + p), (unsigned)q};
-                else spill_candidate(hdr, f.cand_list, f.cand_cap, q, __uint_as_float(sc->xn_bits[q]), v, r_global, seg_start + p);
-            }
-        }
+        mx_admit<WT>(acc, thr, tau, tile, (const_f32p)a.queries + (size_t)q * W, W, seg_start, a.Tp, r_global, (unsigned)q, fl, NFL,
+                     &ctl[S_FRONT], lane, [&](float v, int t) {
+                         spill_candidate(hdr, f.cand_list, f.cand_cap, q, __uint_as_float(sc->xn_bits[q]), v, r_global, t);
+                     });
     };
-    while (u < u_hi) {
-        unsigned ri, sg;
-        decode(u, ri, sg);
-        const int64_t row = a.row0 + (int64_t)ri * a.row_stride;
-        const int seg_start = (int)sg * PSH_SEG;
-        const int r_global = (int)(row + a.r_offset);
+    while (u < uq.hi) {
+        const Unit c = unit_decode(a, u);
+        const int seg_start = c.seg_start();
+        const int r_global = (int)(c.row(a) + a.r_offset);
 
         stage_store(st, tile, nfloat, lane);
-        if (a.dbg_times && tid == 0 && u == u_lo) a.dbg_times[(size_t)blockIdx.x * 8 + 4] = (unsigned long long)wall_clock64();   // first data in the tile
-        {
-            const int nq4 = (nfloat + 3) >> 2;
-#pragma unroll
-            for (int q = 0; q < PSH_NSTAGE; ++q) {
-                const int m = lane + 64 * q;
-                if (q < PSH_NSTAGE - 1 || m < nq4) {
-                    const f32x4 v = st.v[q] * scale;
-                    const f32x4 v2 = v * v;
-                    *reinterpret_cast<f16x4*>(a1 + mx_half(4 * m)) = __builtin_convertvector(v, f16x4);
-                    *reinterpret_cast<f16x4*>(a2 + mx_half(4 * m)) = __builtin_convertvector(v2, f16x4);
-                }
-            }
-        }
+        if (a.dbg_times && tid == 0 && u == uq.lo) a.dbg_times[(size_t)blockIdx.x * 8 + 4] = (unsigned long long)wall_clock64();   // first data in the tile
+        mx_convert(st, a1, a2, scale, nfloat, lane);
         wave_lds_fence();
-        const unsigned un = grab();
-        if (un < u_hi) load_unit(st, un);
+        const unsigned un = uq.grab(lane);
+        if (un < uq.hi) load_unit<ALIGNED>(st, a, unit_decode(a, un), nfloat, lane);
 
-        const int m = lane & 31, hk = lane >> 5;
         f16x8 fa[4];
-        f32x16 acc;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) fa[s] = *reinterpret_cast<const f16x8*>(a2 + mx_half(32 * m + 16 * s + 8 * hk));
-#pragma unroll
-        for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[s], bo[s], acc, 0, 0, 0);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) fa[s] = *reinterpret_cast<const f16x8*>(a1 + mx_half(32 * m + 16 * s + 8 * hk));
+        const f32x16 acc = mx_energies(fa, a2, bo, lane);
+        mx_load_a(fa, a1, lane);
         if constexpr (NQ == 1) {
-#pragma unroll
-            for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[s], bx[s], acc, 0, 0, 0);
-            bool keep = false;                             // NaN-safe: !(t^ > thr)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) keep = keep || !(acc[r] > thr2[0]);
-            if (__any(keep)) admit(acc, 0, thr2[0], tau2[0], seg_start, r_global);
+            const f32x16 aq = mx_mac4(fa, bx, acc);
+            if (mx_any_keep(aq, thr2[0])) admit(aq, 0, thr2[0], tau2[0], seg_start, r_global);
         } else {
             // the window energies are in `acc`; every query adds its own banded product on top of them (the energies are the
             // C operand of its first MFMA: no copy)
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
                 const _Float16* bp = bxl + ((size_t)q * 4 * 64 + (size_t)lane) * 8;
-                f32x16 aq = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[0], *reinterpret_cast<const f16x8*>(bp), acc, 0, 0, 0);
-#pragma unroll
-                for (int s = 1; s < 4; ++s) aq = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[s], *reinterpret_cast<const f16x8*>(bp + (size_t)s * 64 * 8), aq, 0, 0, 0);
-                bool keep = false;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) keep = keep || !(aq[r] > thr2[q]);
-                if (__any(keep)) admit(aq, q, thr2[q], tau2[q], seg_start, r_global);
+                const f32x16 aq = mx_mac4(fa, [&](int s) { return *reinterpret_cast<const f16x8*>(bp + (size_t)s * 64 * 8); }, acc);
+                if (mx_any_keep(aq, thr2[q])) admit(aq, q, thr2[q], tau2[q], seg_start, r_global);
             }
         }
         wave_lds_fence();  // all lanes done with the tile before it is overwritten
@@ -601,11 +506,6 @@ __device__ __forceinline__ void stream_scan_body(const ScanArgs& a, const FusedA
 // K-step s lies at row m + (s >> 1), halves 16 (s & 1) + 8 hk .. + 7 of it: per PAIR of K-steps one pointer moves by one row
 // and every other offset is an immediate -- the slot-rotation layout of the short kernels (mx_half) cost the K-loop 7 vector
 // instructions per step for the address alone, and on this part vector instructions ADD to the matrix cores' time (A.5).
-// inc += (inc of the lane CTRL names, 0 where there is none): one step of a wave scan, a v_add_f32 with a DPP operand
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_addf(float inc) {
-    return inc + __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(inc), CTRL, ROW_MASK, 0xf, true));
-}
 #define PSH_LONG_ROW 40
 #define PSH_LONG_SFLOATS 1280         // fp32 prefix sums of a segment's squares: entries 0 .. SEG + W - 1 <= 1279; the survivors' scratch afterwards
 #define PSH_LONG_QCAP 64              // deferred survivors a wave keeps before it verifies them (8-byte entries)
@@ -665,13 +565,7 @@ __device__ __forceinline__ void stream_scan_long_body(const ScanArgs& a, const F
     const StreamCtl* sc = &hdr->stream;
 
     const int nfloat = PSH_SEG + W - 1;
-    const unsigned n_rs = (unsigned)a.n_rows * (unsigned)a.nseg;
-    const unsigned u_lo = (unsigned)(((u64)n_rs * blockIdx.x) / gridDim.x);
-    const unsigned u_hi = (unsigned)(((u64)n_rs * (blockIdx.x + 1u)) / gridDim.x);
-    auto decode = [&](unsigned uu, unsigned& ri, unsigned& sg) {
-        ri = fast_div(uu, a.magic_nseg, (unsigned)a.nseg);
-        sg = uu - ri * (unsigned)a.nseg;
-    };
+    const UnitQueue uq = unit_queue((unsigned)a.n_rows * (unsigned)a.nseg, &ctl[S_NEXT]);
     // A segment is staged by BUFFER loads (round 6): the row is the resource (base = its first float, records = its bytes), a lane's
     // five 16-byte pieces sit at one constant VGPR offset + immediates, the segment's start is the scalar offset -- no address
     // arithmetic on the vector ALUs, and what lies beyond the row reads as zero (it only feeds inadmissible windows).  Rows need
@@ -679,8 +573,7 @@ __device__ __forceinline__ void stream_scan_long_body(const ScanArgs& a, const F
     const int lane16 = lane * 16;
     auto stage_row = [&](Stage& sx, int64_t row, int seg_start) {
         const int64_t bytes = a.T * 4;
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.dataset + row * a.T), 0,
-                                                                             (int)(bytes > 0x7ffffffc ? 0x7ffffffc : bytes), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs = buffer_rsrc(a.dataset + row * a.T, (unsigned)(bytes > 0x7ffffffc ? 0x7ffffffc : bytes));
         const int nq4 = (nfloat + 3) >> 2;
 #pragma unroll
         for (int q = 0; q < PSH_NSTAGE; ++q)
@@ -690,13 +583,12 @@ __device__ __forceinline__ void stream_scan_long_body(const ScanArgs& a, const F
             }
     };
     auto load_unit = [&](Stage& sx, unsigned uu) {
-        unsigned ri, sg;
-        decode(uu, ri, sg);
-        stage_row(sx, a.row0 + (int64_t)ri * a.row_stride, (int)sg * PSH_SEG);
+        const Unit c = unit_decode(a, uu);
+        stage_row(sx, c.row(a), c.seg_start());
     };
     Stage st;
-    unsigned u = u_lo + (unsigned)wave;
-    if (u < u_hi) load_unit(st, u);
+    unsigned u = uq.lo + (unsigned)wave;
+    if (u < uq.hi) load_unit(st, u);
     // the tables: the sample kernel's fragments of the shifted query (plain loads: an earlier launch on this stream)
     for (int i = tid; i < nks * 64; i += PSH_SCAN_THREADS) {
         const int s = i >> 6, l = i & 63;
@@ -718,11 +610,6 @@ __device__ __forceinline__ void stream_scan_long_body(const ScanArgs& a, const F
     }
     __syncthreads();
     if (armed_w == 0u) return;                                                // uniform: the ranking reports PSH_STATUS_RETRY
-    auto grab = [&]() -> unsigned {
-        int v = 0;
-        if (lane == 0) v = atomicAdd(&ctl[S_NEXT], 1);
-        return u_lo + (unsigned)__builtin_amdgcn_readfirstlane(v);
-    };
     // ---- deferred survivors (round 6).  A window that survives the test goes to the wave's queue -- row, t, query: 8 bytes --
     // and the queue is verified when it is full (64 entries) and when the wave has no unit left: about ten survivors in a wave's
     // whole life on ordinary data, so ONE batch at its end instead of a stall in one segment out of four (re-fetching the segment
@@ -773,11 +660,10 @@ __device__ __forceinline__ void stream_scan_long_body(const ScanArgs& a, const F
     const _Float16* pb0 = bxl + lane * 8;
     const float* ps_lo = sp + m + 128 * hk;                                   // S[p] of the lane's 16 windows: p = m + 128 hk + 32 (r & 3) + 256 (r >> 2)
     const float* ps_hi = ps_lo + W;
-    while (u < u_hi) {
-        unsigned ri, sg;
-        decode(u, ri, sg);
-        const int64_t row = a.row0 + (int64_t)ri * a.row_stride;
-        const int seg_start = (int)sg * PSH_SEG;
+    while (u < uq.hi) {
+        const Unit c = unit_decode(a, u);
+        const int64_t row = c.row(a);
+        const int seg_start = c.seg_start();
         {
             // the segment's f16 copy y^ (rows of 32 samples), and -- round 6 -- the WINDOW ENERGIES from fp32 prefix sums of the
             // squares instead of a second banded product: S[i] = sum of y~_j^2, j < i, 3 adds inside a lane, six DPP adds across
@@ -810,17 +696,17 @@ __device__ __forceinline__ void stream_scan_long_body(const ScanArgs& a, const F
 #endif
             {
 #pragma unroll
-            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_addf<0x111, 0xf>(inc[q]);
+            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_add<0x111, 0xf>(inc[q]);
 #pragma unroll
-            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_addf<0x112, 0xf>(inc[q]);
+            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_add<0x112, 0xf>(inc[q]);
 #pragma unroll
-            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_addf<0x114, 0xf>(inc[q]);
+            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_add<0x114, 0xf>(inc[q]);
 #pragma unroll
-            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_addf<0x118, 0xf>(inc[q]);
+            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_add<0x118, 0xf>(inc[q]);
 #pragma unroll
-            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_addf<0x142, 0xa>(inc[q]);
+            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_add<0x142, 0xa>(inc[q]);
 #pragma unroll
-            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_addf<0x143, 0xc>(inc[q]);
+            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_add<0x143, 0xc>(inc[q]);
             float carry = 0.0f;
 #pragma unroll
             for (int q = 0; q < PSH_NSTAGE; ++q) {
@@ -832,8 +718,8 @@ __device__ __forceinline__ void stream_scan_long_body(const ScanArgs& a, const F
             }
         }
         wave_lds_fence();
-        const unsigned un = grab();
-        if (un < u_hi) load_unit(st, un);
+        const unsigned un = uq.grab(lane);
+        if (un < uq.hi) load_unit(st, un);
 #ifdef PSH_TUNING
         const int nks_run = (a.dbg & 8) ? 1 : nks;                            // ablation: one K-step (results invalid)
 #else
@@ -853,7 +739,7 @@ __device__ __forceinline__ void stream_scan_long_body(const ScanArgs& a, const F
             // last segments for windows that do not exist.
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                if (seg_start + 32 * ((r & 3) + 8 * (r >> 2) + 4 * hk) + m >= a.Tp) ce[r] = __uint_as_float(PSH_INF_BITS);
+                if (seg_start + mx_window(r, lane) >= a.Tp) ce[r] = __uint_as_float(PSH_INF_BITS);
         }
 #ifdef PSH_TUNING
         if (a.dbg & 32) {                                                     // ablation: no energies read back (results invalid)
@@ -893,7 +779,7 @@ __device__ __forceinline__ void stream_scan_long_body(const ScanArgs& a, const F
                 if (!__any(hm != 0u)) continue;
 #pragma unroll 1
                 for (int r = 0; r < 16; ++r) {
-                    const int p = 32 * ((r & 3) + 8 * (r >> 2) + 4 * hk) + m; // C layout: row -> window
+                    const int p = mx_window(r, lane);
                     const bool hit = (((hm >> r) & 1u) != 0u) && (seg_start + p < a.Tp);
                     const unsigned long long mask = __ballot(hit);
                     if (!mask) continue;
@@ -997,17 +883,15 @@ __device__ __forceinline__ void stream_sample_long_body(const ScanArgs& a, const
     }
     const int lane16 = lane * 16;
     auto load_unit = [&](Stage& sx, unsigned uu) {
-        const unsigned ri = fast_div(uu, a.magic_nseg, (unsigned)a.nseg);
-        const unsigned sg = uu - ri * (unsigned)a.nseg;
-        const int64_t row = f.boot_row0 + (int64_t)ri * f.boot_row_stride;
+        const Unit c = unit_decode(a, uu);
+        const int64_t row = f.boot_row0 + (int64_t)c.ri * f.boot_row_stride;
         const int64_t bytes = a.T * 4;
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.dataset + row * a.T), 0,
-                                                                             (int)(bytes > 0x7ffffffc ? 0x7ffffffc : bytes), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs = buffer_rsrc(a.dataset + row * a.T, (unsigned)(bytes > 0x7ffffffc ? 0x7ffffffc : bytes));
         const int nq4 = (nfloat + 3) >> 2;
 #pragma unroll
         for (int q = 0; q < PSH_NSTAGE; ++q)
             if (q < PSH_NSTAGE - 1 || lane + 64 * q < nq4) {
-                const u32x4v w = __builtin_amdgcn_raw_buffer_load_b128(rs, lane16 + 1024 * q, (int)sg * PSH_SEG * 4, 0);
+                const u32x4v w = __builtin_amdgcn_raw_buffer_load_b128(rs, lane16 + 1024 * q, c.seg_start() * 4, 0);
                 sx.v[q] = f32x4{__uint_as_float(w[0]), __uint_as_float(w[1]), __uint_as_float(w[2]), __uint_as_float(w[3])};
             }
     };
@@ -1068,8 +952,8 @@ __device__ __forceinline__ void stream_sample_long_body(const ScanArgs& a, const
     const float* ps_lo = sp + m + 128 * hk;
     const float* ps_hi = ps_lo + W;
     while (u < nbu) {
-        const unsigned ri = fast_div(u, a.magic_nseg, (unsigned)a.nseg);
-        const int seg_start = (int)(u - ri * (unsigned)a.nseg) * PSH_SEG;
+        const Unit c = unit_decode(a, u);
+        const int seg_start = c.seg_start();
         {   // f16 rows and the fp32 prefix sums of the squares (stream_scan_long_body: the construction and its bound are there)
             const int nq4 = (nfloat + 3) >> 2;
             float d0[PSH_NSTAGE], d1[PSH_NSTAGE], d2[PSH_NSTAGE], d3[PSH_NSTAGE], inc[PSH_NSTAGE];
@@ -1084,17 +968,17 @@ __device__ __forceinline__ void stream_sample_long_body(const ScanArgs& a, const
                 inc[q] = d3[q];
             }
 #pragma unroll
-            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_addf<0x111, 0xf>(inc[q]);
+            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_add<0x111, 0xf>(inc[q]);
 #pragma unroll
-            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_addf<0x112, 0xf>(inc[q]);
+            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_add<0x112, 0xf>(inc[q]);
 #pragma unroll
-            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_addf<0x114, 0xf>(inc[q]);
+            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_add<0x114, 0xf>(inc[q]);
 #pragma unroll
-            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_addf<0x118, 0xf>(inc[q]);
+            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_add<0x118, 0xf>(inc[q]);
 #pragma unroll
-            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_addf<0x142, 0xa>(inc[q]);
+            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_add<0x142, 0xa>(inc[q]);
 #pragma unroll
-            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_addf<0x143, 0xc>(inc[q]);
+            for (int q = 0; q < PSH_NSTAGE; ++q) inc[q] = dpp_add<0x143, 0xc>(inc[q]);
             float carry = 0.0f;
 #pragma unroll
             for (int q = 0; q < PSH_NSTAGE; ++q) {
@@ -1131,7 +1015,7 @@ __device__ __forceinline__ void stream_sample_long_body(const ScanArgs& a, const
             } else {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int p = 32 * ((r & 3) + 8 * (r >> 2) + 4 * hk) + m;
+                    const int p = mx_window(r, lane);
                     mn = p < nvalid ? fminf(mn, c[r]) : mn;
                 }
             }
@@ -1149,7 +1033,7 @@ __device__ __forceinline__ void stream_sample_long_body(const ScanArgs& a, const
             const float inv = __uint_as_float((unsigned)(127 - sexp) << 23);
             ub = ub * inv * inv;
             if (!(ub == ub)) ub = __uint_as_float(PSH_INF_BITS);              // NaN data: the unit carries no information
-            if (lane == 0) st_sc1(&hdr->minima[(size_t)q * f.units_stride + u], __float_as_uint(ub));   // write-through
+            if (lane == 0) store_sc1(&hdr->minima[(size_t)q * f.units_stride + u], __float_as_uint(ub));   // write-through
         }
         wave_lds_fence();                                                     // all lanes done with the arrays before they are overwritten
         if (__builtin_amdgcn_readfirstlane(loose ? 1 : 0)) {
@@ -1157,7 +1041,7 @@ __device__ __forceinline__ void stream_sample_long_body(const ScanArgs& a, const
             // rows are dead --, the exact chains of the lane's 16 windows, the exact minimum over the unit
             {
                 Stage s2;
-                stage_load<false>(s2, a.dataset + (f.boot_row0 + (int64_t)ri * f.boot_row_stride) * a.T, a.T, seg_start, nfloat, lane);
+                psh::load_unit<false>(s2, a, f.boot_row0, f.boot_row_stride, c, nfloat, lane);
                 stage_store<false>(s2, sp, nfloat, lane);
             }
             wave_lds_fence();
@@ -1174,7 +1058,7 @@ __device__ __forceinline__ void stream_sample_long_body(const ScanArgs& a, const
 #pragma unroll
                 for (int off = 32; off > 0; off >>= 1) mq = fminf(mq, __shfl_xor(mq, off, 64));
                 if (!(mq == mq)) mq = __uint_as_float(PSH_INF_BITS);
-                if (lane == 0) st_sc1(&hdr->minima[(size_t)q * f.units_stride + u], __float_as_uint(mq));
+                if (lane == 0) store_sc1(&hdr->minima[(size_t)q * f.units_stride + u], __float_as_uint(mq));
             }
             wave_lds_fence();
             {   // (the rows held fp32 samples: every slot a segment does not write must be finite again)
