@@ -624,6 +624,39 @@ int psh_lagged_moments(int device, void* stream, const float* x, int64_t R, int6
                        double* out_sums, int64_t* out_rows_used, int32_t* out_status, void* workspace,
                        size_t workspace_bytes);
 
+/*
+ * The wavelet scattering spectra of an ensemble where it lies (Morel et al., arXiv 2204.10177, in this project's own
+ * terms).  x: device float32, row r starts at x + r * row_stride and holds n samples, n a power of two, 8 <= n <= 4096;
+ * J: scales, 1 <= J <= log2(n) - 2;  psi_hat: device J x n/2 float64, psi_hat[j][k] the real Fourier multiplier of the
+ * analytic wavelet of scale j = 1 .. J at bin k < n/2, taken to be zero outside n / 2^(j+2) < k < n / 2^j and never read
+ * there;  G: row groups, 1 <= G <= R, group g holding rows [floor(g R / G), floor((g+1) R / G)).  Per row, F the DFT of
+ * size n (convolutions are circular), every sample converted to double first, all arithmetic in double:
+ *   W_j = IDFT(F[x] psi_hat[j]),   U_j = |W_j|,   V_{j1,j2} = IDFT(F[U_j1] psi_hat[j2]), j1 <= j2,
+ *   S1[j] = mean_t U_j,   S2[j] = mean_t U_j^2,   C3[j1,j2] = mean_t W_j2 conj(V_{j1,j2}), j1 <= j2,
+ *   C4[j1,j1',j2] = mean_t V_{j1,j2} conj(V_{j1',j2}), j1 <= j1' <= j2.
+ *   out_sums: device G x NOUT float64, NOUT = 2 J + 2 P3 + 2 P4, P3 = J (J + 1) / 2, P4 = J (J + 1) (J + 2) / 6: the sums of
+ *   the per-row values over the group's rows, laid out [S1 (J), S2 (J), Re C3 (P3), Im C3 (P3), Re C4 (P4), Im C4 (P4)]
+ *   with p3 = j2 (j2 - 1) / 2 + (j1 - 1) and p4 = (j2 - 1) j2 (j2 + 1) / 6 + j1' (j1' - 1) / 2 + (j1 - 1);
+ *   out_rows_used: device G int64;  out_status: device int32 (PSH_SCATTERING_STATUS_*), or NULL;
+ *   workspace: device, psh_scattering_spectra_workspace_bytes.
+ * A row that holds a NaN or an inf contributes nothing, is not counted in out_rows_used, and sets
+ * PSH_SCATTERING_STATUS_ROWS_EXCLUDED.  The summation order is fixed by (R, n, J, G) alone (no floating-point atomics, no
+ * dependence on the number of workgroups that ran): two calls give identical bits, and a group's sums depend on its own
+ * rows alone.  Every transform stays in LDS: a row's spectra never go to device memory.
+ * A NULL pointer, R < 1, n not a power of two or n < 8, row_stride < n, J < 1, J > log2(n) - 2, G < 1 or G > R:
+ * PSH_ERR_ARG before anything touches the device; n > 4096 or R >= 2^31 (and, where n is not known, J > 10):
+ * PSH_ERR_UNSUPPORTED; a workspace that is too small: PSH_ERR_WORKSPACE.
+ * The method, in full, heads shadowing_amd/csrc/psh_scattering.hip; shadowing_amd/scattering.py is its numpy twin and
+ * computes the stock wavelets.
+ */
+#define PSH_SCATTERING_STATUS_OK             0
+#define PSH_SCATTERING_STATUS_ROWS_EXCLUDED  1   /* at least one row held a NaN or an inf and was left out */
+/* host only, nothing is launched: the bytes psh_scattering_spectra needs for these sizes */
+int psh_scattering_spectra_workspace_bytes(int64_t R, int J, int64_t G, size_t* out_bytes);
+int psh_scattering_spectra(int device, void* stream, const float* x, int64_t R, int64_t row_stride, int n, int J,
+                           const double* psi_hat, int64_t G, double* out_sums, int64_t* out_rows_used,
+                           int32_t* out_status, void* workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,7 +49,8 @@ EXPORTS = ("psh_version", "psh_strerror", "psh_last_hip_error", "psh_workspace_b
            "psh_comm_destroy", "psh_comm_world", "psh_exchange_merge", "psh_stream_create_reserving", "psh_stream_destroy",
            "psh_weighted_moments", "psh_realized_variance", "psh_count_nonfinite", "psh_smear_nonfinite", "psh_rows_nonfinite",
            "psh_shadow_block_layout", "psh_shadow_blocking", "psh_hedged_mc", "psh_pdv_generate", "psh_mrw_generate", "psh_smrw_generate",
-           "psh_lagged_moments", "psh_lagged_moments_workspace_bytes")
+           "psh_lagged_moments", "psh_lagged_moments_workspace_bytes", "psh_scattering_spectra",
+           "psh_scattering_spectra_workspace_bytes")
 
 _lib = None
 
@@ -165,6 +166,10 @@ def load() -> C.CDLL:
     L.psh_lagged_moments_workspace_bytes.argtypes = [i64, i32, i64, C.POINTER(C.c_size_t)]
     L.psh_lagged_moments.restype = i32
     L.psh_lagged_moments.argtypes = [i32, vp, vp, i64, i64, i32, i32, i64, vp, vp, vp, vp, C.c_size_t]
+    L.psh_scattering_spectra_workspace_bytes.restype = i32
+    L.psh_scattering_spectra_workspace_bytes.argtypes = [i64, i32, i64, C.POINTER(C.c_size_t)]
+    L.psh_scattering_spectra.restype = i32
+    L.psh_scattering_spectra.argtypes = [i32, vp, vp, i64, i64, i32, i32, vp, i64, vp, vp, vp, vp, C.c_size_t]
     L.psh_gather_paths.restype = i32
     L.psh_gather_paths.argtypes = [i32, vp, vp, i64, i64, i64, i64, vp, i64, i32, vp]
     if L.psh_version() != PSH_VERSION:
@@ -997,6 +1002,53 @@ def lagged_moments(x: torch.Tensor, m: int, G: int):
     _check(L.psh_lagged_moments(x.device.index, _stream_ptr(x.device), x.data_ptr(), R, row_stride, n, int(m), int(G),
                                 sums.data_ptr(), rows_used.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel() * 8),
            "psh_lagged_moments")
+    return sums, rows_used, status
+
+
+PSH_SCATTERING_MAX_N = 4096
+PSH_SCATTERING_STATUS_ROWS_EXCLUDED = 1
+
+
+def scattering_nout(J: int) -> int:
+    """NOUT = 2 J + 2 P3 + 2 P4 of psh_scattering_spectra."""
+    return 2 * J + J * (J + 1) + J * (J + 1) * (J + 2) // 3
+
+
+def scattering_spectra_workspace_bytes(R: int, J: int, G: int) -> int:
+    out = C.c_size_t(0)
+    _check(load().psh_scattering_spectra_workspace_bytes(int(R), int(J), int(G), C.byref(out)),
+           "psh_scattering_spectra_workspace_bytes")
+    return out.value
+
+
+def scattering_spectra(x: torch.Tensor, J: int, G: int, psi_hat: torch.Tensor):
+    """psh_scattering_spectra on a float32 HIP tensor (..., n) whose rows lie a constant stride apart (contiguous, a
+    (R, 1, n) ensemble, or a slice of the last dimension of one -- no copy) with the (J, n / 2) float64 multipliers psi_hat
+    on the same device: (sums (G, NOUT) float64, rows_used (G,) int64, status (1,) int32), all on the device; nothing is
+    synchronised here."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise NativeLibraryError(f"x must be a tensor on a HIP device (got {type(x).__name__} on "
+                                 f"{getattr(x, 'device', '?')}); there is no CPU path here")
+    if x.dtype != torch.float32:
+        raise TypeError(f"x must be torch.float32, got {x.dtype}")
+    rows = _uniform_rows(x) if x.numel() else None
+    if rows is None:
+        raise ValueError("x must be non-empty rows of samples a constant stride apart, the last dimension contiguous")
+    R, row_stride = rows
+    n, J, G = x.shape[-1], int(J), int(G)
+    if not (isinstance(psi_hat, torch.Tensor) and psi_hat.device == x.device and psi_hat.dtype == torch.float64
+            and psi_hat.is_contiguous() and tuple(psi_hat.shape) == (J, n // 2)):
+        raise ValueError(f"psi_hat must be a contiguous ({J}, {n // 2}) float64 tensor on {x.device}")
+    L = load()
+    nbytes = C.c_size_t(0)
+    _check(L.psh_scattering_spectra_workspace_bytes(R, J, G, C.byref(nbytes)), "psh_scattering_spectra_workspace_bytes")
+    sums = torch.empty((G, scattering_nout(J)), dtype=torch.float64, device=x.device)
+    rows_used = torch.empty((G,), dtype=torch.int64, device=x.device)
+    status = torch.empty((1,), dtype=torch.int32, device=x.device)
+    ws = torch.empty((max(nbytes.value, 8) + 7) // 8, dtype=torch.int64, device=x.device)
+    _check(L.psh_scattering_spectra(x.device.index, _stream_ptr(x.device), x.data_ptr(), R, row_stride, n, J,
+                                    psi_hat.data_ptr(), G, sums.data_ptr(), rows_used.data_ptr(), status.data_ptr(),
+                                    ws.data_ptr(), ws.numel() * 8), "psh_scattering_spectra")
     return sums, rows_used, status
 
 

@@ -1566,4 +1566,46 @@ int psh_lagged_moments(int device, void* stream, const float* x, int64_t R, int6
     return PSH_OK;
 }
 
+// the argument checks both psh_scattering_spectra entry points share, and the plan (units, outputs) for the sizes
+static int scattering_spectra_plan(int64_t R, int J, int64_t G, ScatArgs* a, size_t* bytes) {
+    if (R < 1 || J < 1 || G < 1 || G > R) return PSH_ERR_ARG;
+    if (J > PSH_SCAT_MAX_J || R >= ((int64_t)1 << 31)) return PSH_ERR_UNSUPPORTED;        // (g * R stays in int64)
+    scattering_plan(R, G, J, a);
+    const int64_t units = G * a->upg;
+    if (units >= ((int64_t)1 << 31)) return PSH_ERR_UNSUPPORTED;                          // (one workgroup per unit)
+    *bytes = (size_t)units * ((size_t)a->nout * sizeof(double) + sizeof(int64_t));
+    return PSH_OK;
+}
+
+int psh_scattering_spectra_workspace_bytes(int64_t R, int J, int64_t G, size_t* out_bytes) {
+    if (!out_bytes) return PSH_ERR_ARG;
+    ScatArgs a{};
+    return scattering_spectra_plan(R, J, G, &a, out_bytes);
+}
+
+int psh_scattering_spectra(int device, void* stream, const float* x, int64_t R, int64_t row_stride, int n, int J,
+                           const double* psi_hat, int64_t G, double* out_sums, int64_t* out_rows_used,
+                           int32_t* out_status, void* workspace, size_t workspace_bytes) {
+    if (!x || !psi_hat || !out_sums || !out_rows_used || !workspace || n < 8 || (n & (n - 1)) != 0 || row_stride < n ||
+        R < 1 || J < 1 || G < 1 || G > R)
+        return PSH_ERR_ARG;
+    int logn = 3;
+    while (logn < 30 && (1 << logn) < n) ++logn;
+    if (J > logn - 2) return PSH_ERR_ARG;
+    if (n > PSH_SCAT_MAX_N) return PSH_ERR_UNSUPPORTED;
+    ScatArgs a{};
+    size_t need = 0;
+    const int rc = scattering_spectra_plan(R, J, G, &a, &need);
+    if (rc != PSH_OK) return rc;
+    if (R > INT64_MAX / row_stride) return PSH_ERR_ARG;
+    if (workspace_bytes < need) return PSH_ERR_WORKSPACE;
+    a.x = x; a.R = R; a.stride = row_stride; a.G = G; a.n = n; a.logn = logn; a.J = J; a.psi = psi_hat;
+    a.partial = (double*)workspace;
+    a.unit_rows = (int64_t*)(a.partial + G * a.upg * (int64_t)a.nout);
+    a.out = out_sums; a.rows_used = out_rows_used; a.status = out_status;
+    GUARD_DEVICE(device);
+    HIP_TRY(launch_scattering(a, (hipStream_t)stream));
+    return PSH_OK;
+}
+
 }  // extern "C"

@@ -467,4 +467,23 @@ struct MomentsLagArgs {
 void moments_lag_plan(int64_t R, int64_t G, int m, MomentsLagArgs* a);
 hipError_t launch_lagged_moments(const MomentsLagArgs& a, hipStream_t s);
 
+// psh_scattering.hip: wavelet scattering spectra over groups of rows (psh_scattering_spectra)
+#define PSH_SCAT_MAX_N 4096   // the working buffer of n complex doubles, F[x] and the kept envelope spectra stay in LDS
+#define PSH_SCAT_MAX_J 10     // log2(PSH_SCAT_MAX_N) - 2
+#define PSH_SCAT_MAX_NOUT 570 // 2 J + J (J + 1) + J (J + 1) (J + 2) / 3 at J = 10
+struct ScatArgs {
+    const float* x;           // R rows of n samples, stride floats apart
+    int64_t R, stride, G;     // group g holds rows [floor(g R / G), floor((g+1) R / G))
+    int n, logn, J, nout;     // n = 2^logn; nout = 2 J + 2 P3 + 2 P4
+    int64_t upg;              // units per group on the grid (scattering_plan: a function of R and G alone)
+    const double* psi;        // (J, n / 2) Fourier multipliers, read inside n / 2^(j+2) < k < n / 2^j alone
+    double* partial;          // workspace: (G * upg, nout) ...
+    int64_t* unit_rows;       // ... then (G * upg) rows used
+    double* out;              // (G, nout)
+    int64_t* rows_used;       // (G)
+    int32_t* status;          // PSH_SCATTERING_STATUS_*, or nullptr
+};
+void scattering_plan(int64_t R, int64_t G, int J, ScatArgs* a);
+hipError_t launch_scattering(const ScatArgs& a, hipStream_t s);
+
 }  // namespace psh
