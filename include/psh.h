@@ -657,6 +657,30 @@ int psh_scattering_spectra(int device, void* stream, const float* x, int64_t R, 
                            const double* psi_hat, int64_t G, double* out_sums, int64_t* out_rows_used,
                            int32_t* out_status, void* workspace, size_t workspace_bytes);
 
+/*
+ * The gradient of each row's scattering spectra with respect to the row (a vector-Jacobian product).  x, R, row_stride, n,
+ * J, psi_hat, G, the group bounds and the NOUT layout are psh_scattering_spectra's;  cot: device G x NOUT float64, the
+ * cotangent of each group's sums;  out_grad: device float64, row r at out_grad + r * grad_stride, grad_stride >= n (what
+ * lies between the rows is left untouched).  For row r of group g, with out_o(x_r) the row's own value of output o (what
+ * the row adds to its group's sum), every sample converted to double first and all arithmetic in double:
+ *   out_grad[r * grad_stride + t] = sum_o cot[g][o] d out_o(x_r) / d x_r[t].
+ * A row that holds a NaN or an inf gets n zeros and sets PSH_SCATTERING_STATUS_ROWS_EXCLUDED in out_status (device int32,
+ * or NULL).  The cotangent of Im C4[j1, j1, j2] is ignored: that output is identically 0.  Where W_j(t) = 0 the phase
+ * W / |W| is taken as 0, so an all-zero row gets an all-zero gradient and never a NaN.
+ * A row's gradient depends on that row and on its group's cot row alone: two calls give identical bits, and the bits do
+ * not depend on R, G, the row's position or how many workgroups ran (no atomics).  Every transform stays in LDS.
+ *   workspace: device, psh_scattering_vjp_workspace_bytes.
+ * The argument checks and error codes are psh_scattering_spectra's, and grad_stride < n is PSH_ERR_ARG too.
+ * The formulas and the method head shadowing_amd/csrc/psh_scattering_grad.hip; the torch twin in
+ * shadowing_amd/scattering.py (torch.fft on the time-domain definition, differentiated by autograd) is an independent
+ * derivation.
+ */
+/* host only, nothing is launched: the bytes psh_scattering_vjp needs for these sizes */
+int psh_scattering_vjp_workspace_bytes(int64_t R, int n, int J, int64_t G, size_t* out_bytes);
+int psh_scattering_vjp(int device, void* stream, const float* x, int64_t R, int64_t row_stride, int n, int J,
+                       const double* psi_hat, int64_t G, const double* cot /* G x NOUT */, double* out_grad,
+                       int64_t grad_stride, int32_t* out_status, void* workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,7 +17,8 @@ from .pdv import AutoregressiveLinearPredictor, PDVModel, PDVModelDiscrete
 from .pricing import PriceData, Smile, compute_smile
 from .statistics import realized_variance
 from .stylized import LaggedMoments, fit_smrw, lagged_moments
-from .scattering import ScatteringSpectra, scattering_bank, scattering_spectra
+from .scattering import (ScatteringSpectra, scattering_bank, scattering_generate, scattering_loss, scattering_spectra,
+                         scattering_sums)
 
 __all__ = [
     "ArrayType", "ContextManagerBase", "PredictionContext", "ImputationContext", "CrossChannelContext",
@@ -27,6 +28,7 @@ __all__ = [
     "PDVModel", "PDVModelDiscrete", "AutoregressiveLinearPredictor",
     "MRWGenerator", "mrw_log_returns", "SMRWGenerator", "smrw_log_returns", "smrw_kernel", "smrw_leverage",
     "smrw_sq_moment", "LaggedMoments", "lagged_moments", "fit_smrw",
-    "ScatteringSpectra", "scattering_spectra", "scattering_bank",
+    "ScatteringSpectra", "scattering_spectra", "scattering_bank", "scattering_sums", "scattering_loss",
+    "scattering_generate",
 ]
 __version__ = "0.1.0"

@@ -50,7 +50,7 @@ EXPORTS = ("psh_version", "psh_strerror", "psh_last_hip_error", "psh_workspace_b
            "psh_weighted_moments", "psh_realized_variance", "psh_count_nonfinite", "psh_smear_nonfinite", "psh_rows_nonfinite",
            "psh_shadow_block_layout", "psh_shadow_blocking", "psh_hedged_mc", "psh_pdv_generate", "psh_mrw_generate", "psh_smrw_generate",
            "psh_lagged_moments", "psh_lagged_moments_workspace_bytes", "psh_scattering_spectra",
-           "psh_scattering_spectra_workspace_bytes")
+           "psh_scattering_spectra_workspace_bytes", "psh_scattering_vjp", "psh_scattering_vjp_workspace_bytes")
 
 _lib = None
 
@@ -170,6 +170,10 @@ def load() -> C.CDLL:
     L.psh_scattering_spectra_workspace_bytes.argtypes = [i64, i32, i64, C.POINTER(C.c_size_t)]
     L.psh_scattering_spectra.restype = i32
     L.psh_scattering_spectra.argtypes = [i32, vp, vp, i64, i64, i32, i32, vp, i64, vp, vp, vp, vp, C.c_size_t]
+    L.psh_scattering_vjp_workspace_bytes.restype = i32
+    L.psh_scattering_vjp_workspace_bytes.argtypes = [i64, i32, i32, i64, C.POINTER(C.c_size_t)]
+    L.psh_scattering_vjp.restype = i32
+    L.psh_scattering_vjp.argtypes = [i32, vp, vp, i64, i64, i32, i32, vp, i64, vp, vp, i64, vp, vp, C.c_size_t]
     L.psh_gather_paths.restype = i32
     L.psh_gather_paths.argtypes = [i32, vp, vp, i64, i64, i64, i64, vp, i64, i32, vp]
     if L.psh_version() != PSH_VERSION:
@@ -1050,6 +1054,46 @@ def scattering_spectra(x: torch.Tensor, J: int, G: int, psi_hat: torch.Tensor):
                                     psi_hat.data_ptr(), G, sums.data_ptr(), rows_used.data_ptr(), status.data_ptr(),
                                     ws.data_ptr(), ws.numel() * 8), "psh_scattering_spectra")
     return sums, rows_used, status
+
+
+def scattering_vjp(x: torch.Tensor, J: int, G: int, psi_hat: torch.Tensor, cot: torch.Tensor, out: torch.Tensor | None = None):
+    """psh_scattering_vjp on the rows psh_scattering_spectra takes (same x, J, G, psi_hat) with the cotangent cot (G, NOUT)
+    float64 of the group sums: (grad (R, n) float64, status (1,) int32) on the device, grad[r] the gradient of
+    sum_o cot[group of r][o] out_o(x_r) with respect to row r.  out: a float64 (R, >= n) tensor whose rows lie a constant
+    stride apart, written in place on its first n columns (the rest is left untouched).  Nothing is synchronised here."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise NativeLibraryError(f"x must be a tensor on a HIP device (got {type(x).__name__} on "
+                                 f"{getattr(x, 'device', '?')}); there is no CPU path here")
+    if x.dtype != torch.float32:
+        raise TypeError(f"x must be torch.float32, got {x.dtype}")
+    rows = _uniform_rows(x) if x.numel() else None
+    if rows is None:
+        raise ValueError("x must be non-empty rows of samples a constant stride apart, the last dimension contiguous")
+    R, row_stride = rows
+    n, J, G = x.shape[-1], int(J), int(G)
+    if not (isinstance(psi_hat, torch.Tensor) and psi_hat.device == x.device and psi_hat.dtype == torch.float64
+            and psi_hat.is_contiguous() and tuple(psi_hat.shape) == (J, n // 2)):
+        raise ValueError(f"psi_hat must be a contiguous ({J}, {n // 2}) float64 tensor on {x.device}")
+    nout = scattering_nout(J)
+    if not (isinstance(cot, torch.Tensor) and cot.device == x.device and cot.dtype == torch.float64
+            and cot.is_contiguous() and tuple(cot.shape) == (G, nout)):
+        raise ValueError(f"cot must be a contiguous ({G}, {nout}) float64 tensor on {x.device}")
+    if out is None:
+        grad, grad_stride = torch.empty((R, n), dtype=torch.float64, device=x.device), n
+    else:
+        if not (isinstance(out, torch.Tensor) and out.device == x.device and out.dtype == torch.float64 and out.dim() == 2
+                and out.shape[0] == R and out.shape[1] >= n and out.stride(1) == 1 and (R == 1 or out.stride(0) >= n)):
+            raise ValueError(f"out must be a ({R}, >= {n}) float64 tensor on {x.device}, its last dimension contiguous")
+        grad, grad_stride = out[:, :n], (out.stride(0) if R > 1 else max(out.shape[1], n))
+    L = load()
+    nbytes = C.c_size_t(0)
+    _check(L.psh_scattering_vjp_workspace_bytes(R, n, J, G, C.byref(nbytes)), "psh_scattering_vjp_workspace_bytes")
+    status = torch.empty((1,), dtype=torch.int32, device=x.device)
+    ws = torch.empty((max(nbytes.value, 8) + 7) // 8, dtype=torch.int64, device=x.device)
+    _check(L.psh_scattering_vjp(x.device.index, _stream_ptr(x.device), x.data_ptr(), R, row_stride, n, J,
+                                psi_hat.data_ptr(), G, cot.data_ptr(), grad.data_ptr(), grad_stride, status.data_ptr(),
+                                ws.data_ptr(), ws.numel() * 8), "psh_scattering_vjp")
+    return grad, status
 
 
 def hedged_mc(dlnx: torch.Tensor, weights: torch.Tensor | None, Ts, Ms, x_init: float = 100.0, rate: float = 0.0,

@@ -1608,4 +1608,43 @@ int psh_scattering_spectra(int device, void* stream, const float* x, int64_t R, 
     return PSH_OK;
 }
 
+// the argument checks both psh_scattering_vjp entry points share (the forward's), log2(n) and the workspace for the sizes
+static int scattering_vjp_plan(int64_t R, int n, int J, int64_t G, int* logn_out, size_t* bytes) {
+    if (n < 8 || (n & (n - 1)) != 0 || R < 1 || J < 1 || G < 1 || G > R) return PSH_ERR_ARG;
+    int logn = 3;
+    while (logn < 30 && (1 << logn) < n) ++logn;
+    if (J > logn - 2) return PSH_ERR_ARG;
+    if (n > PSH_SCAT_MAX_N || R >= ((int64_t)1 << 31)) return PSH_ERR_UNSUPPORTED;          // ((r + 1) * G stays in int64)
+    *logn_out = logn;
+    *bytes = (size_t)scattering_grad_workgroups(R) * sizeof(int32_t);
+    return PSH_OK;
+}
+
+int psh_scattering_vjp_workspace_bytes(int64_t R, int n, int J, int64_t G, size_t* out_bytes) {
+    if (!out_bytes) return PSH_ERR_ARG;
+    int logn = 0;
+    return scattering_vjp_plan(R, n, J, G, &logn, out_bytes);
+}
+
+int psh_scattering_vjp(int device, void* stream, const float* x, int64_t R, int64_t row_stride, int n, int J,
+                       const double* psi_hat, int64_t G, const double* cot, double* out_grad, int64_t grad_stride,
+                       int32_t* out_status, void* workspace, size_t workspace_bytes) {
+    if (!x || !psi_hat || !cot || !out_grad || !workspace || row_stride < n || grad_stride < n) return PSH_ERR_ARG;
+    int logn = 0;
+    size_t need = 0;
+    const int rc = scattering_vjp_plan(R, n, J, G, &logn, &need);
+    if (rc != PSH_OK) return rc;
+    if (R > INT64_MAX / row_stride || R > INT64_MAX / grad_stride) return PSH_ERR_ARG;
+    if (workspace_bytes < need) return PSH_ERR_WORKSPACE;
+    ScatGradArgs a{};
+    a.x = x; a.R = R; a.stride = row_stride; a.G = G; a.n = n; a.logn = logn; a.J = J;
+    a.nout = 2 * J + J * (J + 1) + J * (J + 1) * (J + 2) / 3;
+    a.wgs = scattering_grad_workgroups(R);
+    a.psi = psi_hat; a.cot = cot; a.grad = out_grad; a.gstride = grad_stride;
+    a.flags = (int32_t*)workspace; a.status = out_status;
+    GUARD_DEVICE(device);
+    HIP_TRY(launch_scattering_grad(a, (hipStream_t)stream));
+    return PSH_OK;
+}
+
 }  // extern "C"

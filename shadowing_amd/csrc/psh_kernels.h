@@ -486,4 +486,21 @@ struct ScatArgs {
 void scattering_plan(int64_t R, int64_t G, int J, ScatArgs* a);
 hipError_t launch_scattering(const ScatArgs& a, hipStream_t s);
 
+// psh_scattering_grad.hip: the gradient of each row's scattering spectra with respect to the row (psh_scattering_vjp)
+#define PSH_SCATGRAD_MAX_WGS 1024   // workgroup w takes rows w, w + wgs, ..
+struct ScatGradArgs {
+    const float* x;           // R rows of n samples, stride floats apart
+    int64_t R, stride, G;     // group g holds rows [floor(g R / G), floor((g+1) R / G))
+    int n, logn, J, nout;     // as ScatArgs
+    int wgs;                  // scattering_grad_workgroups(R)
+    const double* psi;        // (J, n / 2), as ScatArgs
+    const double* cot;        // (G, nout): the cotangent of each group's sums
+    double* grad;             // R rows of n doubles, gstride doubles apart
+    int64_t gstride;
+    int32_t* flags;           // workspace: (wgs) 1 where the workgroup left a row out
+    int32_t* status;          // PSH_SCATTERING_STATUS_*, or nullptr
+};
+int scattering_grad_workgroups(int64_t R);
+hipError_t launch_scattering_grad(const ScatGradArgs& a, hipStream_t s);
+
 }  // namespace psh

@@ -20,6 +20,13 @@ On a HIP float32 tensor the sums are psh_scattering_spectra's (the method heads 
 uses the Fourier-domain forms of C3 and C4): the ensemble is read in place, every transform stays in LDS and only the
 (G, NOUT) sums come to the host.  `cuda=False` is the numpy float64 twin: np.fft on the time-domain sums above, on
 float32-rounded inputs.
+
+Generating from them (scattering_generate): `scattering_sums` is the same measurement made differentiable in the rows -- on a
+HIP float32 tensor a torch.autograd.Function over psh_scattering_spectra and psh_scattering_vjp (the gradient kernel heads
+shadowing_amd/csrc/psh_scattering_grad.hip), on a CPU tensor a torch float64 twin (torch.fft on the time-domain definition,
+differentiated by autograd: an independent derivation) -- `scattering_loss` the squared distance of a batch's mean values to
+a target's in the normalisations of phi1 .. phi4 frozen at the target, and `scattering_generate` gradient descent from white
+noise on that loss, batch by batch.  It is this project's counterpart of scatspectra's `generate`; parity is not pinned.
 """
 from __future__ import annotations
 
@@ -247,4 +254,240 @@ def scattering_spectra(x, J: int | None = None, groups: int | None = None, cuda:
     return _summarise(sums, rows, R, n, J)
 
 
-__all__ = ["ScatteringSpectra", "scattering_spectra", "scattering_bank"]
+def _torch_row_values(x, psi):
+    """(r, NOUT) float64 torch: _row_values in torch ops (x (r, n) float64, psi (J, n) float64 padded with zeros), so that
+    autograd differentiates the time-domain definition.  torch's abs has the gradient sgn: 0 where W_j(t) = 0."""
+    import torch
+    n = x.shape[-1]
+    J = psi.shape[0]
+    W = torch.fft.ifft(torch.fft.fft(x, dim=-1)[:, None, :] * psi, dim=-1)     # (r, J, n)
+    U = W.abs()
+    FU = torch.fft.fft(U, dim=-1)
+    c3, c4 = [], []
+    for j2 in range(1, J + 1):
+        V = torch.fft.ifft(FU[:, :j2, :] * psi[j2 - 1], dim=-1)                # (r, j1 = 1 .. j2, n)
+        c3.append((W[:, j2 - 1, None, :] * V.conj()).mean(dim=-1))             # (r, j1): p3 runs on with j2, then j1
+        a4 = torch.einsum("rat,rbt->rab", V, V.conj()) / n                     # (r, j1, j1')
+        c4.extend(a4[:, :j1p, j1p - 1] for j1p in range(1, j2 + 1))            # p4 runs on with j2, j1', then j1
+    c3, c4 = torch.cat(c3, dim=1), torch.cat(c4, dim=1)
+    real4 = torch.tensor([0.0 if j1 == j1p else 1.0 for j2 in range(1, J + 1) for j1p in range(1, j2 + 1)
+                          for j1 in range(1, j1p + 1)], dtype=x.dtype, device=x.device)       # Im C4[j1, j1, j2] = 0
+    return torch.cat([U.mean(dim=-1), (U * U).mean(dim=-1), c3.real, c3.imag, c4.real, c4.imag * real4], dim=1)
+
+
+def _torch_sums(x, bank, G: int):
+    """The torch float64 twin of psh_scattering_spectra on (R, n), differentiable in x: (sums (G, NOUT), rows (G,) int64)."""
+    import torch
+    R, n = x.shape
+    x = x.to(torch.float64)
+    x = x + (x.to(torch.float32).to(torch.float64) - x).detach()               # the kernels read float32 (the gradient stays float64)
+    psi = torch.zeros((bank.shape[0], n), dtype=torch.float64, device=x.device)
+    psi[:, :n // 2] = torch.as_tensor(bank, dtype=torch.float64, device=x.device)
+    ok = torch.isfinite(x).all(dim=1)
+    vals = _torch_row_values(torch.where(ok[:, None], x, torch.zeros((), dtype=x.dtype, device=x.device)), psi) * ok[:, None]
+    bounds = group_bounds(R, G)
+    group = torch.as_tensor(np.repeat(np.arange(G), np.diff(bounds)), device=x.device)
+    sums = torch.zeros((G, vals.shape[1]), dtype=torch.float64, device=x.device).index_add(0, group, vals)
+    rows = torch.zeros((G,), dtype=torch.int64, device=x.device).index_add(0, group, ok.to(torch.int64))
+    return sums, rows
+
+
+_DeviceSums = None
+
+
+def _device_sums_function():
+    """The torch.autograd.Function over psh_scattering_spectra and psh_scattering_vjp (made on first use: torch is imported
+    lazily here)."""
+    global _DeviceSums
+    if _DeviceSums is None:
+        import torch
+        from . import _native
+
+        class DeviceSums(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, x, J, G, psi):
+                sums, rows, _ = _native.scattering_spectra(x, J, G, psi)
+                ctx.save_for_backward(x, psi)
+                ctx.J, ctx.G = J, G
+                ctx.mark_non_differentiable(rows)
+                return sums, rows
+
+            @staticmethod
+            def backward(ctx, cot, _rows):
+                x, psi = ctx.saved_tensors
+                grad, _ = _native.scattering_vjp(x, ctx.J, ctx.G, psi, cot.to(torch.float64).contiguous())
+                return grad.to(torch.float32), None, None, None
+
+        _DeviceSums = DeviceSums
+    return _DeviceSums
+
+
+def scattering_sums(x, J: int | None = None, groups: int | None = None, bank=None):
+    """(sums (G, NOUT) float64, rows (G,) int64) of a torch ensemble x, (R, n) or (R, 1, n): the group sums
+    scattering_spectra summarises (ScatteringSpectra.group_sums, .group_rows), as torch tensors where x lies and
+    differentiable in x.  On a HIP tensor: psh_scattering_spectra forward, psh_scattering_vjp backward (x is rounded to
+    float32 if it is not float32; the gradient is float32; n <= 4096; no host fallback).  On a CPU tensor: the torch float64
+    twin on float32-rounded rows.  J, groups and bank as scattering_spectra."""
+    import torch
+    if not _is_torch(x):
+        raise TypeError(f"x must be a torch tensor, got {type(x).__name__}")
+    if x.ndim == 3 and x.shape[1] == 1:
+        x = x[:, 0, :]
+    if x.ndim != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"x must be (R, n) or (R, 1, n) and not empty, got shape {tuple(x.shape)}")
+    R, n = int(x.shape[0]), int(x.shape[1])
+    J = _check_n_J(n, J)
+    G = min(R, DEFAULT_GROUPS) if groups is None else groups
+    if isinstance(G, bool) or int(G) != G or not 1 <= G <= R:
+        raise ValueError(f"groups must be an integer with 1 <= groups <= R = {R}, got {groups!r}")
+    G = int(G)
+    if bank is None:
+        host_bank = None
+    else:
+        host_bank = bank.detach().cpu().numpy() if _is_torch(bank) else np.asarray(bank)
+        if host_bank.shape != (J, n // 2) or not np.isrealobj(host_bank):
+            raise ValueError(f"bank must be real and ({J}, {n // 2}), got shape {tuple(host_bank.shape)}")
+        host_bank = np.ascontiguousarray(host_bank, dtype=np.float64)
+    if x.is_cuda:
+        if n > MAX_N_DEVICE:
+            raise ValueError(f"cuda=True takes rows of n <= {MAX_N_DEVICE} samples (got {n}): the transforms of a longer row "
+                             f"leave LDS; slice the ensemble, e.g. x[..., :{MAX_N_DEVICE}], or use cuda=False")
+        if x.dtype != torch.float32:
+            x = x.to(torch.float32)
+        psi = _device_bank(n, J, x.device) if host_bank is None else torch.from_numpy(host_bank).to(x.device)
+        return _device_sums_function().apply(x, J, G, psi)
+    return _torch_sums(x, scattering_bank(n, J) if host_bank is None else host_bank, G)
+
+
+def _normalisers(J: int, sigma2: np.ndarray) -> np.ndarray:
+    """(NOUT,) the factors s_o that turn S1, S2, C3, C4 into phi1 .. phi4 at a fixed sigma2 (phi2 relative to sigma2)."""
+    root = np.sqrt(sigma2)
+    P3, P4 = J * (J + 1) // 2, J * (J + 1) * (J + 2) // 6
+    s3, s4 = np.empty(P3), np.empty(P4)
+    for j2 in range(1, J + 1):
+        for j1 in range(1, j2 + 1):
+            s3[pair_index(j1, j2)] = 1.0 / (root[j1 - 1] * root[j2 - 1])
+            for j1p in range(j1, j2 + 1):
+                s4[triple_index(j1, j1p, j2)] = 1.0 / (root[j1 - 1] * root[j1p - 1])
+    return np.concatenate([1.0 / root, 1.0 / sigma2, s3, s3, s4, s4])
+
+
+def _loss_terms(target: ScatteringSpectra):
+    """(T (NOUT,), s (NOUT,)) float64 numpy: the target's per-row means and the normalisers frozen at its sigma2."""
+    if not isinstance(target, ScatteringSpectra):
+        raise TypeError(f"target must be a ScatteringSpectra, got {type(target).__name__}")
+    if target.rows_used < 1:
+        raise ValueError("the target has no rows: every row it was measured on held a NaN or an inf")
+    T = target.group_sums.sum(axis=0) / float(target.rows_used)
+    sigma2 = T[target.J:2 * target.J]
+    if not (np.all(np.isfinite(sigma2)) and np.all(sigma2 > 0)):
+        raise ValueError("the target has no power at some scale (sigma2 = 0 or not finite): nothing to normalise with")
+    return T, _normalisers(target.J, sigma2)
+
+
+def _loss(sums, rows, T, s):
+    m = sums.sum(dim=0) / rows.sum()
+    return ((s * (m - T)) ** 2).mean()
+
+
+def scattering_loss(sums, rows, target: ScatteringSpectra):
+    """The squared distance of a batch to a target, a 0-dim float64 torch tensor, differentiable in sums:
+        loss = (1 / NOUT) sum_o (s_o (m_o - T_o))^2,   m = sums.sum(0) / rows.sum(),   T = the target's per-row means,
+    with s_o the normalisations of phi1 .. phi4 frozen at the target's sigma2 = T[S2]: 1 / sqrt(sigma2[j]) for S1,
+    1 / sigma2[j] for S2, 1 / sqrt(sigma2[j1] sigma2[j2]) for both parts of C3 and 1 / sqrt(sigma2[j1] sigma2[j1']) for both
+    parts of C4.  sums, rows: scattering_sums' (the target's J).  The loss is quadratic in the sums."""
+    import torch
+    T, s = _loss_terms(target)
+    if tuple(sums.shape[1:]) != (T.size,):
+        raise ValueError(f"sums must be (G, {T.size}) for the target's J = {target.J}, got shape {tuple(sums.shape)}")
+    return _loss(sums, rows, torch.as_tensor(T, device=sums.device), torch.as_tensor(s, device=sums.device))
+
+
+def start_variance(target: ScatteringSpectra) -> float:
+    """The variance of the white noise a generation starts from: sum_j phi2[j] / sum_{j,k} (psi_hat[j][k]^2 / n), the level
+    at which white noise has the target's total wavelet power (E S2[j] = variance sum_k psi_hat[j][k]^2 / n)."""
+    bank = scattering_bank(target.n, target.J)
+    return float(np.sum(target.phi2) / (np.sum(bank * bank) / target.n))
+
+
+class _Stop(Exception):
+    pass
+
+
+def scattering_generate(target, R: int, batch: int = 256, max_eval: int = 200, tol: float = 1e-3, seed: int = 0,
+                        cuda: bool | None = None, return_info: bool = False):
+    """(R, 1, n) float32 log-returns that carry the scattering spectra of `target`: a ScatteringSpectra (n and J are its own;
+    the stock wavelets), or data that scattering_spectra measures first.  A torch tensor, on the HIP device under cuda=True
+    (cuda=None: when one is present; rows of n <= 4096, no host fallback), the layout PathShadowing takes as `dataset`.
+
+    Each batch of `batch` rows is its own problem.  Start: torch.randn from a CPU generator seeded with (seed, batch index),
+    scaled to start_variance(target).  Descent: torch.optim.LBFGS (strong_wolfe, history 20) on a float64 master copy that
+    is rounded to float32 at every evaluation, because the kernels read float32, on scattering_loss of the batch with
+    one group per row.  Stop: sqrt(loss) <= tol, or max_eval evaluations; the rows returned are the float32 rows of the
+    evaluation with the smallest loss.  return_info=True returns (rows, info) with info["initial_loss"], ["final_loss"]
+    and ["evaluations"], one entry per batch."""
+    import torch
+    if not isinstance(target, ScatteringSpectra):
+        target = scattering_spectra(target, cuda=cuda)
+    for name, v in (("R", R), ("batch", batch), ("max_eval", max_eval)):
+        if isinstance(v, bool) or int(v) != v or v < 1:
+            raise ValueError(f"{name} must be a positive integer, got {v!r}")
+    R, batch, max_eval, n = int(R), int(batch), int(max_eval), int(target.n)
+    J = _check_n_J(n, target.J)
+    T_host, s_host = _loss_terms(target)
+    if cuda is None:
+        cuda = torch.cuda.is_available()
+    if cuda:
+        from . import _native
+        if not torch.cuda.is_available():
+            raise _native.NativeLibraryError("cuda=True needs a HIP device, and there is no host fallback under it")
+        if n > MAX_N_DEVICE:
+            raise ValueError(f"cuda=True takes rows of n <= {MAX_N_DEVICE} samples (got {n}): the transforms of a longer row "
+                             f"leave LDS; slice the ensemble, e.g. x[..., :{MAX_N_DEVICE}], or use cuda=False")
+    dev = torch.device("cuda" if cuda else "cpu")
+    T, s = torch.as_tensor(T_host, device=dev), torch.as_tensor(s_host, device=dev)
+    std = float(np.sqrt(start_variance(target)))
+    out = torch.empty((R, 1, n), dtype=torch.float32, device=dev)
+    info = {"initial_loss": [], "final_loss": [], "evaluations": []}
+    for b, r0 in enumerate(range(0, R, batch)):
+        rows = min(batch, R - r0)
+        gen = torch.Generator().manual_seed(int(np.random.SeedSequence([int(seed), b]).generate_state(2, np.uint32)
+                                                .view(np.uint64)[0] >> 1))
+        master = (torch.randn((rows, n), generator=gen, dtype=torch.float64) * std).to(dev).requires_grad_(True)
+        opt = torch.optim.LBFGS([master], lr=1.0, max_iter=max_eval, max_eval=max_eval, history_size=20,
+                                tolerance_grad=0.0, tolerance_change=0.0, line_search_fn="strong_wolfe")
+        state = {"evals": 0, "first": None, "best": float("inf"), "rows": None}
+
+        def closure():
+            opt.zero_grad()
+            x32 = master.to(torch.float32)
+            sums, used = scattering_sums(x32 if cuda else x32.to(torch.float64), J, groups=rows)
+            loss = _loss(sums, used, T, s)
+            loss.backward()
+            value = float(loss.detach())
+            state["evals"] += 1
+            if state["first"] is None:
+                state["first"] = value
+            if value < state["best"]:
+                state["best"], state["rows"] = value, x32.detach().clone()
+            if not np.isfinite(value) or np.sqrt(value) <= tol or state["evals"] >= max_eval:
+                raise _Stop
+            return loss
+
+        try:
+            while state["evals"] < max_eval:
+                before = state["evals"]
+                opt.step(closure)
+                if state["evals"] == before:
+                    break
+        except _Stop:
+            pass
+        out[r0:r0 + rows, 0, :] = state["rows"]
+        info["initial_loss"].append(state["first"])
+        info["final_loss"].append(state["best"])
+        info["evaluations"].append(state["evals"])
+    return (out, info) if return_info else out
+
+
+__all__ = ["ScatteringSpectra", "scattering_spectra", "scattering_bank", "scattering_sums", "scattering_loss",
+           "scattering_generate"]
