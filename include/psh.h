@@ -506,6 +506,34 @@ int psh_realized_variance(int device, void* stream, const float* x, int64_t n_ro
                           const int* Ts, int nT, int vol, float* out);
 
 /*
+ * Weighted quantiles and tail means over the k shadowing paths: VaR and expected shortfall of the conditional ensemble.
+ * One column is one (b, i) of values (device B x k x m float32); its weights are weights[b, 0 .. k-1] (device B x k
+ * float64, AS GIVEN, never renormalised), or NULL: w_j = 1.  levels: HOST array of n_levels <= PSH_QUANTILE_MAX_LEVELS
+ * levels 0 < p < 1, in any order.  With the k paths ordered by (value ascending, path index ascending), x_(i) and w_(i) the
+ * sorted values and weights, all arithmetic in double and the float32 values converted exactly:
+ *   C_i = sum_{l<=i} w_(l)     S_i = sum_{l<=i} w_(l) x_(l)     W = C_{k-1} (as computed)     t = p * W
+ *   i*  = the first i with C_i >= t
+ *   out_q     = x_(i*)                                                   the lower weighted quantile (inverted CDF)
+ *   out_lower = ( S_{i*-1} + (t - C_{i*-1}) x_(i*) ) / t                 mean of the lowest p of the mass
+ *   out_upper = ( (C_{i*} - t) x_(i*) + (S_{k-1} - S_{i*}) ) / (W - t)   mean of the highest 1 - p of the mass
+ * out_q, out_lower, out_upper: device B x n_levels x m float64;  out_status: device B int32 (PSH_QUANTILE_STATUS_* bits),
+ * or NULL.  A path of weight exactly 0 contributes nothing, whatever its value.  A non-finite value at a positive weight:
+ * the column's results are NaN, PSH_QUANTILE_STATUS_NONFINITE.  A non-finite or negative weight, or W not > 0: all the
+ * query's results are NaN, PSH_QUANTILE_STATUS_WEIGHTS.  -0.0 and +0.0 are equal values; which zero a quantile returns is
+ * unspecified.  No floating-point atomics: two calls give identical bits, and so do weights scaled by a power of two.
+ * A NULL values, levels or output, B, k, m or n_levels < 1, n_levels > PSH_QUANTILE_MAX_LEVELS, or a level that is not
+ * inside (0, 1): PSH_ERR_ARG before anything touches the device; k > PSH_MAX_K or B * m >= 2^31: PSH_ERR_UNSUPPORTED.
+ * The method heads shadowing_amd/csrc/psh_quantiles.hip; shadowing_amd/quantiles.py is its numpy twin.
+ */
+#define PSH_QUANTILE_MAX_LEVELS 32
+#define PSH_QUANTILE_STATUS_OK         0
+#define PSH_QUANTILE_STATUS_NONFINITE  1   /* a path with positive weight has a non-finite value in some column */
+#define PSH_QUANTILE_STATUS_WEIGHTS    2   /* a non-finite or negative weight, or a weight sum that is not > 0 */
+int psh_weighted_quantiles(int device, void* stream, const float* values, const double* weights, int B, int k, int m,
+                           const double* levels, int n_levels, double* out_q, double* out_lower, double* out_upper,
+                           int32_t* out_status);
+
+/*
  * Hedged Monte Carlo (Potters, Bouchaud, Sestovic 2001) on the k shadowing paths of each of B dates: the option prices,
  * Black-Scholes implied vols and strikes of a smile.  The method, in full, heads shadowing_amd/csrc/psh_hmc.hip (and
  * README "Option pricing"); shadowing_amd/pricing.py is its numpy twin.

@@ -15,6 +15,7 @@ from .mrw import (MRWGenerator, SMRWGenerator, mrw_log_returns, smrw_kernel, smr
                   smrw_sq_moment)
 from .pdv import AutoregressiveLinearPredictor, PDVModel, PDVModelDiscrete
 from .pricing import PriceData, Smile, compute_smile
+from .quantiles import PredictiveQuantiles, weighted_quantiles
 from .statistics import realized_variance
 from .stylized import LaggedMoments, fit_smrw, lagged_moments
 from .scattering import (ScatteringSpectra, scattering_bank, scattering_generate, scattering_loss, scattering_spectra,
@@ -29,6 +30,6 @@ __all__ = [
     "MRWGenerator", "mrw_log_returns", "SMRWGenerator", "smrw_log_returns", "smrw_kernel", "smrw_leverage",
     "smrw_sq_moment", "LaggedMoments", "lagged_moments", "fit_smrw",
     "ScatteringSpectra", "scattering_spectra", "scattering_bank", "scattering_sums", "scattering_loss",
-    "scattering_generate",
+    "scattering_generate", "PredictiveQuantiles", "weighted_quantiles",
 ]
 __version__ = "0.1.0"

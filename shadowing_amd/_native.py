@@ -50,7 +50,8 @@ EXPORTS = ("psh_version", "psh_strerror", "psh_last_hip_error", "psh_workspace_b
            "psh_weighted_moments", "psh_realized_variance", "psh_count_nonfinite", "psh_smear_nonfinite", "psh_rows_nonfinite",
            "psh_shadow_block_layout", "psh_shadow_blocking", "psh_hedged_mc", "psh_pdv_generate", "psh_mrw_generate", "psh_smrw_generate",
            "psh_lagged_moments", "psh_lagged_moments_workspace_bytes", "psh_scattering_spectra",
-           "psh_scattering_spectra_workspace_bytes", "psh_scattering_vjp", "psh_scattering_vjp_workspace_bytes")
+           "psh_scattering_spectra_workspace_bytes", "psh_scattering_vjp", "psh_scattering_vjp_workspace_bytes",
+           "psh_weighted_quantiles")
 
 _lib = None
 
@@ -148,6 +149,8 @@ def load() -> C.CDLL:
     L.psh_smear_nonfinite.argtypes = [i32, vp, vp, i64, i64, i64, i32, i32, vp]
     L.psh_weighted_moments.restype = i32
     L.psh_weighted_moments.argtypes = [i32, vp, vp, vp, i32, i32, i32, vp, vp]
+    L.psh_weighted_quantiles.restype = i32
+    L.psh_weighted_quantiles.argtypes = [i32, vp, vp, vp, i32, i32, i32, C.POINTER(C.c_double), i32, vp, vp, vp, vp]
     L.psh_realized_variance.restype = i32
     L.psh_realized_variance.argtypes = [i32, vp, vp, i64, i64, i32, C.POINTER(C.c_int), i32, i32, vp]
     L.psh_hedged_mc.restype = i32
@@ -931,6 +934,38 @@ def weighted_moments(values: torch.Tensor, weights: torch.Tensor | None):
     _check(load().psh_weighted_moments(v.device.index, _stream_ptr(v.device), v.data_ptr(), w_ptr, B, k, m,
                                        mean.data_ptr(), std.data_ptr()), "psh_weighted_moments")
     return mean, std
+
+
+PSH_QUANTILE_MAX_LEVELS = 32
+PSH_QUANTILE_STATUS_OK, PSH_QUANTILE_STATUS_NONFINITE, PSH_QUANTILE_STATUS_WEIGHTS = 0, 1, 2
+
+
+def weighted_quantiles(values: torch.Tensor, weights: torch.Tensor | None, levels):
+    """psh_weighted_quantiles over axis 1 of a (B, k, ...) float32 statistic with (B, k) float64 weights (None: unit
+    weights) at the levels 0 < p < 1: (q, lower, upper), each (B, Q, ...) float64, and status (B,) int32, all on the device;
+    nothing is synchronised here."""
+    v = _dev_tensor(values, torch.float32, "values")
+    if v.dim() < 2:
+        raise ValueError("values must be (B, k, ...)")
+    B, k = v.shape[:2]
+    m = v.numel() // (B * k) if B * k else 0
+    if m == 0:
+        raise ValueError("values is empty")
+    lv = [float(p) for p in levels]
+    w_ptr = None
+    if weights is not None:
+        w = _dev_tensor(weights, torch.float64, "weights")
+        if tuple(w.shape) != (B, k):
+            raise ValueError(f"weights must be (B, k) = ({B}, {k}), got {tuple(w.shape)}")
+        w_ptr = w.data_ptr()
+    shape = (B, len(lv)) + tuple(v.shape[2:])
+    q, lower, upper = (torch.empty(shape, dtype=torch.float64, device=v.device) for _ in range(3))
+    status = torch.empty((B,), dtype=torch.int32, device=v.device)
+    arr = (C.c_double * max(len(lv), 1))(*lv)
+    _check(load().psh_weighted_quantiles(v.device.index, _stream_ptr(v.device), v.data_ptr(), w_ptr, B, k, m, arr, len(lv),
+                                         q.data_ptr(), lower.data_ptr(), upper.data_ptr(), status.data_ptr()),
+           "psh_weighted_quantiles")
+    return q, lower, upper, status
 
 
 def _uniform_rows(x: torch.Tensor):

@@ -1437,6 +1437,26 @@ int psh_realized_variance(int device, void* stream, const float* x, int64_t n_ro
     return PSH_OK;
 }
 
+int psh_weighted_quantiles(int device, void* stream, const float* values, const double* weights, int B, int k, int m,
+                           const double* levels, int n_levels, double* out_q, double* out_lower, double* out_upper,
+                           int32_t* out_status) {
+    if (!values || !levels || !out_q || !out_lower || !out_upper || B <= 0 || k <= 0 || m <= 0 || n_levels <= 0 ||
+        n_levels > PSH_QUANTILE_MAX_LEVELS)
+        return PSH_ERR_ARG;
+    QuantileArgs a{};
+    for (int i = 0; i < n_levels; ++i) {
+        if (!(levels[i] > 0.0 && levels[i] < 1.0)) return PSH_ERR_ARG;      // (NaN fails both)
+        a.levels[i] = levels[i];
+    }
+    if (k > PSH_MAX_K || (int64_t)B * m >= ((int64_t)1 << 31)) return PSH_ERR_UNSUPPORTED;   // (one workgroup per column)
+    a.values = values; a.weights = weights; a.B = B; a.k = k; a.m = m; a.n_levels = n_levels;
+    a.q = out_q; a.lower = out_lower; a.upper = out_upper; a.status = out_status;
+    GUARD_DEVICE(device);
+    if (out_status) HIP_TRY(hipMemsetAsync(out_status, 0, (size_t)B * sizeof(int32_t), (hipStream_t)stream));
+    HIP_TRY(launch_quantiles(a, (hipStream_t)stream));
+    return PSH_OK;
+}
+
 int psh_hedged_mc(int device, void* stream, const float* dlnx, int64_t row_stride, int B, int k, int len,
                   const double* weights, double x_init, double rate, const int* Ts, int nT, const double* Ms, int nM,
                   int degree, int kind, double* out_price, double* out_iv, double* out_strike, double* out_sigma,

@@ -380,6 +380,19 @@ hipError_t launch_smear_nonfinite(const float* ds, int64_t R, int64_t C, int64_t
 hipError_t launch_moments(const MomentsArgs& a, hipStream_t s);
 hipError_t launch_realized_variance(const RvArgs& a, hipStream_t s);
 
+// psh_quantiles.hip: weighted quantiles and tail means over the k paths (psh_weighted_quantiles)
+struct QuantileArgs {
+    const float* values;      // (B, k, m)
+    const double* weights;    // (B, k), or nullptr: w = 1
+    int B, k, m, n_levels;
+    double levels[32];        // PSH_QUANTILE_MAX_LEVELS
+    double* q;                // (B, n_levels, m), as lower and upper
+    double* lower;
+    double* upper;
+    int32_t* status;          // (B), zeroed by the caller, or nullptr
+};
+hipError_t launch_quantiles(const QuantileArgs& a, hipStream_t s);
+
 // psh_hmc.hip: hedged Monte Carlo on the shadowing paths of a date (psh_hedged_mc)
 #define PSH_HMC_SG 3              // strikes a block solves (the Gram matrix of a step is shared by them)
 #define PSH_HMC_MAX_T 64

@@ -143,6 +143,7 @@ class PathShadowing:
         self.last_profile = None
         self.last_path = None       # "hip" / "torch": which implementation served the last shadow() / predict()
         self.last_predict_reduction = None   # device_predict: "device" (psh_weighted_moments) / "host" (the class's own avg / std)
+        self.last_quantile_reduction = None  # predict_quantiles: "device" (psh_weighted_quantiles) / "host" (the numpy twin)
 
     @staticmethod
     def _load_with_scatspectra(dataset):
@@ -806,17 +807,10 @@ class PathShadowing:
         values = to_predict(future)
         return proba.avg(values, axis=1), proba.std(values, axis=1)
 
-    def _predict_on_device(self, x: torch.Tensor, y: torch.Tensor, k: int, to_predict: Callable,
-                           proba_name: str, eta: float | None):
-        """shadow() + predict_from_paths() with the PATHS kept on the GPU: the k paths of every query (74 MB for
-        the tutorial's call) stay in HBM and `to_predict` is evaluated there on the device tensor of their
-        out-context; what crosses PCIe are the (B, k) distances -- the installed DiscreteProba turns them into its weights
-        on the host (ref :245-250: scatspectra's classes when that package is importable, the stand-ins of averaging.py
-        otherwise; no formula of theirs is restated) -- and the (B, ...) moments: `avg` / `std` over the k paths
-        (ref :251-252) are reduced on the device by psh_weighted_moments when the class's own avg / std are the weighted
-        moments of weights it exposes (moment_weights checks that on a probe; `last_predict_reduction` says which way a
-        call went); any other class receives the (B, k, ...) statistic on the host and reduces it itself.  Only called
-        when the caller opted in (see predict())."""
+    def _scan_and_evaluate(self, x: torch.Tensor, y: torch.Tensor, k: int, to_predict: Callable):
+        """The prologue of every device-side prediction: the native scan, the path gather and `to_predict` on the device
+        tensor of the out-context.  Returns (values (B, k, ...) on the device, distances (B, k) on the host): the paths
+        never leave HBM."""
         length = x.shape[-1] + self.context.get_out_times()
 
         def evaluate(d, idx, ds):
@@ -844,6 +838,20 @@ class PathShadowing:
             d, idx, ds = out
             values = evaluate(d, idx, ds)
             (d_host,) = self._to_host(d)
+        return values, d_host
+
+    def _predict_on_device(self, x: torch.Tensor, y: torch.Tensor, k: int, to_predict: Callable,
+                           proba_name: str, eta: float | None):
+        """shadow() + predict_from_paths() with the PATHS kept on the GPU: the k paths of every query (74 MB for
+        the tutorial's call) stay in HBM and `to_predict` is evaluated there on the device tensor of their
+        out-context; what crosses PCIe are the (B, k) distances -- the installed DiscreteProba turns them into its weights
+        on the host (ref :245-250: scatspectra's classes when that package is importable, the stand-ins of averaging.py
+        otherwise; no formula of theirs is restated) -- and the (B, ...) moments: `avg` / `std` over the k paths
+        (ref :251-252) are reduced on the device by psh_weighted_moments when the class's own avg / std are the weighted
+        moments of weights it exposes (moment_weights checks that on a probe; `last_predict_reduction` says which way a
+        call went); any other class receives the (B, k, ...) statistic on the host and reduces it itself.  Only called
+        when the caller opted in (see predict())."""
+        values, d_host = self._scan_and_evaluate(x, y, k, to_predict)
         # what has crossed PCIe so far: the (B, k) distances.  The installed class turns them into weights on the host (its
         # formula is its own); if its avg / std ARE the weighted moments of those weights -- checked on a probe, the class
         # stays authoritative -- the (B, k, ...) statistic is reduced where it is (psh_weighted_moments) and only the
@@ -896,6 +904,62 @@ class PathShadowing:
                 self._scan_rows = self._dirty_split = None          # (they keep the per-call upload alive)
             self._predict_scope = None
         return np.concatenate(means), np.concatenate(stds)
+
+    # ------------------------------------------------------------------ predictive quantiles (README "Predictive quantiles")
+    def _quantile_weights(self, proba_name: str, distances: np.ndarray, eta: float | None):
+        """The (B, k) weights of the installed averaging class (None: unit weights), as smile() takes them.  A class that
+        does not expose `weights` cannot weigh a quantile: nothing of it is restated here."""
+        proba = self.init_averaging_proba(proba_name, distances, eta)
+        if not hasattr(proba, "weights"):
+            raise TypeError(f"{type(proba).__name__} exposes no `weights`: weighted quantiles need the weights themselves")
+        return self._smile_weights(proba_name, distances, eta)
+
+    def quantiles_from_paths(self, distances: np.ndarray, paths, to_predict: Callable, levels,
+                             proba_name: str = "softmax", eta: float | None = None):
+        """Weighted quantiles and tail means over the k paths of `to_predict(out-context)`, weighted as
+        predict_from_paths() weighs its mean: a quantiles.PredictiveQuantiles.  Numpy paths take the numpy twin, HIP tensors
+        psh_weighted_quantiles."""
+        from .quantiles import weighted_quantiles
+        values = to_predict(self.context.select_out_context(paths))
+        d = distances.detach().cpu().numpy() if isinstance(distances, torch.Tensor) else np.asarray(distances)
+        return weighted_quantiles(values, self._quantile_weights(proba_name, d, eta), levels)
+
+    def predict_quantiles(self, x_context: ArrayType, k: int, to_predict: Callable, levels, eta: float | None = None,
+                          proba_name: str = "softmax", n_dataset_splits: int = 1, n_context_splits: int = 1,
+                          cuda: bool = False, device_predict: bool | None = None):
+        """shadow() + quantiles_from_paths() over `n_context_splits` batches of queries: predict()'s twin for the quantiles
+        and tail means of the conditional distribution, with the same opt-in rule for `device_predict`.  With cuda=True,
+        device_predict=True on a natively scanned configuration the paths and the statistic stay in HBM: the (B, k)
+        distances come down, the weights go up, and only the three (B, Q, ...) results come back
+        (`last_quantile_reduction` says "device" or "host")."""
+        from .quantiles import PredictiveQuantiles, weighted_quantiles
+        x = _torch(_dim_array(x_context))
+        n = x.shape[0]
+        y = None
+        if device_predict is None:
+            device_predict = bool(getattr(to_predict, "accepts_torch", False))
+        parts = []
+        self._predict_scope = (self.dataset, None) if cuda else None
+        try:
+            for rows in torch.arange(n).split(max(1, n // n_context_splits)):
+                if cuda and device_predict and k <= _native.PSH_MAX_K:
+                    y = self._dataset_tensor() if y is None else y
+                    if self._native_ok(x[rows, ...], y, k):
+                        values, d_host = self._scan_and_evaluate(x[rows, ...], y, k, to_predict)
+                        w = self._quantile_weights(proba_name, d_host, eta)
+                        on_device = values.is_cuda and values.dtype == torch.float32
+                        self.last_quantile_reduction = "device" if on_device else "host"
+                        parts.append(weighted_quantiles(values, w, levels, cuda=on_device))
+                        continue
+                d, paths, _ = self.shadow(x[rows, ...], k, n_dataset_splits, cuda)
+                self.last_quantile_reduction = "host"
+                parts.append(self.quantiles_from_paths(d, paths, to_predict, levels, proba_name, eta))
+        finally:
+            if self._predict_scope is not None and self._predict_scope[1] is not None:
+                self._scan_rows = self._dirty_split = None          # (they keep the per-call upload alive)
+            self._predict_scope = None
+        cat = lambda name: np.concatenate([getattr(p, name) for p in parts])   # noqa: E731
+        return PredictiveQuantiles(parts[0].levels, cat("q"), cat("lower"), cat("upper"), cat("status"))
 
     # ------------------------------------------------------------------ option pricing (README "Option pricing")
     def _smile_weights(self, proba_name: str, distances: np.ndarray, eta: float | None):
