@@ -240,6 +240,49 @@ int psh_scan_topk(int device, void* stream,
                   void* workspace, size_t workspace_bytes, psh_profile* profile);
 
 /*
+ * A resident f16 copy of an ensemble that stays where it is from call to call, and the one-query overlap scan that
+ * streams it instead of the fp32 samples (psh_stream_copy.hip: half the bytes of the pass; results are psh_scan_topk's,
+ * bit for bit -- the copy only feeds the rejection test, the exact chains read the ensemble).
+ *
+ * psh_filter_copy_bytes: host arithmetic.  The copy is a 64-byte header, then R rows of *pitch_halves f16 values:
+ * T rounded up to whole segments of 1024, plus 32 (a 16-byte load of a segment's 1024 + 32 halves never leaves its
+ * row; the tail of a row is zero).
+ * psh_filter_copy_build: enqueues three launches on `stream` -- the sum of squares of the finite samples (per-block
+ * partial sums added in a fixed order: two builds give identical bits), ONE power-of-two exponent e_c for the ensemble
+ * (its rms times 2^e_c lies in [0.5, 1); 0 for an rms that is zero or not finite) written into the header ON THE
+ * DEVICE, and the rows (f16)(y 2^e_c), round to nearest even; what is not a finite f16 is stored as a NaN.  `out`:
+ * out_bytes >= *bytes, 16-byte aligned; `scratch`: PSH_FILTER_COPY_SCRATCH_BYTES, free again when the launches have run.
+ * Nothing is read back: the call never synchronises.
+ * psh_scan_topk_copy: psh_scan_topk with a descriptor of such a copy OF THE SAME `dataset`.  The copy serves exactly one
+ * route -- one query, W <= 33, PSH_FLAG_OVERLAP, no PSH_FLAG_FILTER_VALU / PSH_FLAG_NO_FUSE (a tau_hint is fine) --; every other
+ * call, and a NULL descriptor, behaves as psh_scan_topk does.  copy->served says which: 1 = the copy scan was
+ * launched (psh_profile.path is 3, sample rows and grid as on the fp32 route), 0 = the call went the ordinary way and
+ * copy->reason says why.  Every window that survives the rejection test has its copy values audited against its fp32
+ * samples; a mismatch (the copy is of other data) makes the call report PSH_STATUS_RETRY: rerun it through the
+ * separate launches and drop the copy.  Only survivors are audited: keeping the copy in step with edits of the
+ * ensemble is the caller's business.
+ */
+#define PSH_FILTER_COPY_SCRATCH_BYTES 16384
+#define PSH_COPY_SERVED     0   /* psh_filter_copy.reason */
+#define PSH_COPY_NOT_ROUTE  1   /* not the one-query overlap route with W <= 33 */
+#define PSH_COPY_MISMATCH   2   /* the descriptor does not describe a copy of an (R, T) ensemble */
+typedef struct psh_filter_copy {
+    const void* copy;          /* what psh_filter_copy_build wrote */
+    int64_t pitch_halves;      /* as psh_filter_copy_bytes gives it */
+    int64_t R, T;              /* the ensemble the copy was built from */
+    int served;                /* out */
+    int reason;                /* out: PSH_COPY_* */
+} psh_filter_copy;
+int psh_filter_copy_bytes(int64_t R, int64_t T, size_t* bytes, int64_t* pitch_halves);
+int psh_filter_copy_build(int device, void* stream, const float* dataset, int64_t R, int64_t T,
+                          void* out, size_t out_bytes, void* scratch, size_t scratch_bytes);
+int psh_scan_topk_copy(int device, void* stream,
+                       const float* dataset, int64_t R, int64_t T, int64_t r_offset,
+                       const float* queries, const float* qnorm, int B, int W, int h, int k,
+                       float* out_d, int32_t* out_idx, int32_t* out_status,
+                       void* workspace, size_t workspace_bytes, psh_profile* profile, psh_filter_copy* copy);
+
+/*
  * Same contract, no sampling and no admission threshold: the dataset is
  * processed in row chunks whose every window fits the candidate buffer.
  * Always exact (any amount of ties), several times slower.  out_status is

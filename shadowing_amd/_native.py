@@ -25,6 +25,11 @@ PSH_HMC_MAX_T = PSH_HMC_MAX_M = 64
 FLAG_UNSORTED, FLAG_FILTER_VALU, FLAG_EMBED_DENSE, FLAG_ROWS_GENERIC, FLAG_NO_FUSE, FLAG_RESERVE_CUS, FLAG_EMBED_MX, FLAG_EMBED_TAPS, FLAG_EMBED_PLAN_KEEP, FLAG_EMBED_MX_SPLIT, FLAG_SELECT_ONE_BLOCK, FLAG_OVERLAP, FLAG_MQ_F16, FLAG_LONG_LOOP = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192
 
 
+# psh_filter_copy.reason (include/psh.h)
+PSH_COPY_SERVED, PSH_COPY_NOT_ROUTE, PSH_COPY_MISMATCH = 0, 1, 2
+PSH_FILTER_COPY_SCRATCH_BYTES = 16384
+
+
 class NativeLibraryError(RuntimeError):
     """The HIP extension is missing or failed."""
 
@@ -41,6 +46,11 @@ class PshProfile(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name not in skip}
 
 
+class PshFilterCopy(C.Structure):
+    _fields_ = [("copy", C.c_void_p), ("pitch_halves", C.c_int64), ("R", C.c_int64), ("T", C.c_int64),
+                ("served", C.c_int), ("reason", C.c_int)]
+
+
 EXPORTS = ("psh_version", "psh_strerror", "psh_last_hip_error", "psh_workspace_bytes", "psh_query_norm",
            "psh_scan_topk", "psh_scan_topk_exhaustive", "psh_scan_topk_embedded",
            "psh_scan_topk_embedded_exhaustive", "psh_merge_workspace_bytes", "psh_merge_topk",
@@ -51,7 +61,7 @@ EXPORTS = ("psh_version", "psh_strerror", "psh_last_hip_error", "psh_workspace_b
            "psh_shadow_block_layout", "psh_shadow_blocking", "psh_hedged_mc", "psh_pdv_generate", "psh_mrw_generate", "psh_smrw_generate",
            "psh_lagged_moments", "psh_lagged_moments_workspace_bytes", "psh_scattering_spectra",
            "psh_scattering_spectra_workspace_bytes", "psh_scattering_vjp", "psh_scattering_vjp_workspace_bytes",
-           "psh_weighted_quantiles")
+           "psh_weighted_quantiles", "psh_filter_copy_bytes", "psh_filter_copy_build", "psh_scan_topk_copy")
 
 _lib = None
 
@@ -114,6 +124,12 @@ def load() -> C.CDLL:
     L.psh_scan_topk.argtypes = scan_args
     L.psh_scan_topk_exhaustive.restype = i32
     L.psh_scan_topk_exhaustive.argtypes = scan_args
+    L.psh_scan_topk_copy.restype = i32
+    L.psh_scan_topk_copy.argtypes = scan_args + [C.POINTER(PshFilterCopy)]
+    L.psh_filter_copy_bytes.restype = i32
+    L.psh_filter_copy_bytes.argtypes = [i64, i64, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]
+    L.psh_filter_copy_build.restype = i32
+    L.psh_filter_copy_build.argtypes = [i32, vp, vp, i64, i64, vp, C.c_size_t, vp, C.c_size_t]
     emb_args = [i32, vp, vp, i64, i64, i64, vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, C.c_size_t,
                 C.POINTER(PshProfile)]
     L.psh_scan_topk_embedded.restype = i32
@@ -255,11 +271,112 @@ def query_norm(queries: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def filter_copy_bytes(R: int, T: int) -> tuple[int, int]:
+    """(bytes, pitch_halves) of the resident f16 filter copy of an (R, T) ensemble (psh_filter_copy_bytes: host arithmetic)."""
+    nbytes, pitch = C.c_size_t(0), C.c_int64(0)
+    _check(load().psh_filter_copy_bytes(R, T, C.byref(nbytes), C.byref(pitch)), "psh_filter_copy_bytes")
+    return int(nbytes.value), int(pitch.value)
+
+
+class FilterCopy:
+    """A resident f16 copy of an (R, T) float32 ensemble for the one-query overlap scan (psh_filter_copy_build, include/psh.h):
+    R * T * 2 bytes of device memory more, half the bytes of every such scan.  Owns the buffer and the completion event of its
+    build; a stream other than the builder's waits on that event until it has completed, and every stream is made known to
+    the caching allocator on first use (record_stream).  The copy knows nothing of later edits of the ensemble: whoever keeps
+    it decides when it is stale (the "auto" policy of scan_topk watches the tensor's version counter)."""
+
+    def __init__(self, rows: torch.Tensor):
+        rows = _dev_tensor(rows, torch.float32, "rows")
+        if rows.dim() != 2:
+            raise ValueError("rows must be (R, T)")
+        R, T = rows.shape
+        dev = rows.device
+        nbytes, pitch = filter_copy_bytes(R, T)
+        self.R, self.T, self.pitch_halves, self.nbytes, self.device = R, T, pitch, nbytes, dev
+        self.buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        scratch = torch.empty(PSH_FILTER_COPY_SCRATCH_BYTES, dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        _check(load().psh_filter_copy_build(dev.index, stream.cuda_stream, rows.data_ptr(), R, T, self.buf.data_ptr(), nbytes,
+                                            scratch.data_ptr(), scratch.numel()), "psh_filter_copy_build")
+        self.event = torch.cuda.Event()
+        self.event.record(stream)
+        self._builder = stream.cuda_stream
+        self._streams = {self._builder}
+        self._built = False                  # the event has been seen complete: nobody waits any more
+        self.desc = PshFilterCopy(self.buf.data_ptr(), pitch, R, T, 0, 0)
+
+    def use(self, stream: "torch.cuda.Stream") -> None:
+        """Call before enqueueing a scan that reads the copy on `stream`."""
+        sp = stream.cuda_stream
+        if sp not in self._streams:
+            self.buf.record_stream(stream)
+            self._streams.add(sp)
+        if not self._built and sp != self._builder:
+            if self.event.query():
+                self._built = True
+            else:
+                stream.wait_event(self.event)
+
+
+# ---- scan_topk(filter_copy="auto"): one entry per ensemble, kept as long as the tensor lives
+FILTER_COPY_POLICY = "second"      # "off" | "second" (build on the second consecutive eligible call) | "first"
+_FILTER_COPY_HEADROOM = 1 << 30    # device memory that must stay free beside a new copy
+_filter_copies: dict = {}          # id(base tensor) -> entry
+_filter_copy_builder = FilterCopy  # (tests put fakes here and in the two probes below)
+_filter_copy_capturing = lambda: torch.cuda.is_current_stream_capturing()         # noqa: E731
+_filter_copy_free_bytes = lambda device: torch.cuda.mem_get_info(device)[0]       # noqa: E731
+
+
+def _filter_copy_enabled() -> bool:
+    import os
+    return FILTER_COPY_POLICY in ("second", "first") and os.environ.get("PSH_FILTER_COPY", "1") != "0"
+
+
+def _filter_copy_key(ds: torch.Tensor):
+    base = ds._base if ds._base is not None else ds
+    return base, (ds.data_ptr(), tuple(ds.shape), tuple(ds.stride()), str(ds.device), ds._version)
+
+
+def filter_copy_forget(tensor: torch.Tensor) -> None:
+    """Drop the "auto" copy of `tensor`'s ensemble: after an edit torch cannot see (.data, DLPack, raw pointers)."""
+    base = tensor._base if tensor._base is not None else tensor
+    _filter_copies.pop(id(base), None)
+
+
+def _filter_copy_auto(ds: torch.Tensor):
+    """The "auto" policy: the FilterCopy that serves this call, or None.  One entry per base tensor (it dies with the
+    tensor); a call whose key -- data pointer, shape, strides, device, version counter -- differs from the entry's starts over.
+    The copy is built on the second consecutive eligible call with one key ("second"; "first": at once), if the device has
+    room for it and 1 GiB more, and never while the stream is capturing."""
+    import weakref
+    base, key = _filter_copy_key(ds)
+    ent = _filter_copies.get(id(base))
+    if ent is not None and ent["ref"]() is base and ent["key"] == key:
+        if ent["copy"] is not None:
+            return ent["copy"]
+        ent["calls"] += 1
+    else:
+        bid = id(base)
+        ent = {"key": key, "calls": 1, "copy": None, "denied": False,
+               "ref": weakref.ref(base, lambda _r, bid=bid: _filter_copies.pop(bid, None))}
+        _filter_copies[bid] = ent
+    if ent["denied"] or ent["calls"] < (1 if FILTER_COPY_POLICY == "first" else 2):
+        return None
+    if _filter_copy_capturing():
+        return None
+    nbytes, _ = filter_copy_bytes(ds.shape[0], ds.shape[1])
+    if _filter_copy_free_bytes(ds.device) < nbytes + _FILTER_COPY_HEADROOM:
+        ent["denied"] = True               # (asked once per key: mem_get_info is a driver call)
+        return None
+    ent["copy"] = _filter_copy_builder(ds)
+    return ent["copy"]
+
+
 def scan_topk(dataset: torch.Tensor, queries: torch.Tensor, k: int, h: int = 0, r_offset: int = 0,
               qnorm: torch.Tensor | None = None, workspace: Workspace | None = None,
               exhaustive: bool = False, profile: bool = False, extra_workspace_factor: float = 1.0,
               scan_events: tuple | None = None, out: tuple | None = None, unsorted: bool = False, flags: int = 0,
-              info: dict | None = None, tau_hint: torch.Tensor | None = None):
+              info: dict | None = None, tau_hint: torch.Tensor | None = None, filter_copy="auto"):
     """Enqueue the scan on the current stream.
 
     dataset (R, T) float32 device, queries (B, W) float32 device.  Returns
@@ -275,6 +392,10 @@ def scan_topk(dataset: torch.Tensor, queries: torch.Tensor, k: int, h: int = 0, 
     overlap-friendly launches; ...) without any synchronisation.
     `tau_hint`: (B,) float32 device tensor, the caller's admission levels on acc = (d ||x||)^2 (psh_profile.tau_hint): no
     bootstrap sample; a status other than OK then means "rerun without the hint".
+    `filter_copy`: a FilterCopy of `dataset`, None, or "auto" (default) -- the one-query overlap scan (B = 1, W <= 33,
+    FLAG_OVERLAP) streams a resident f16 copy of the ensemble, built on the second consecutive such call on the same
+    unchanged tensor (FILTER_COPY_POLICY, PSH_FILTER_COPY=0, filter_copy_forget; INTEGRATION.md).  Results do not depend on it;
+    `info` receives `copy_served` / `copy_reason`.
     """
     ds = _dev_tensor(dataset, torch.float32, "dataset")
     q = _dev_tensor(queries, torch.float32, "queries")
@@ -334,14 +455,29 @@ def scan_topk(dataset: torch.Tensor, queries: torch.Tensor, k: int, h: int = 0, 
             prof.mode = 1                 # no events given: nothing is recorded, nothing is synchronised
         prof.flags = flags
         prof.tau_hint = None if tau_hint is None else tau_hint.data_ptr()
-    fn = load().psh_scan_topk_exhaustive if exhaustive else load().psh_scan_topk
-    rc = fn(dev.index, _stream_ptr(dev), ds.data_ptr(), R, T, r_offset, q.data_ptr(),
+    # the resident f16 copy serves one route only: everything else does not even look for one
+    fc = None
+    if filter_copy is not None and B == 1 and W <= 33 and (flags & FLAG_OVERLAP) and not (flags & (FLAG_FILTER_VALU | FLAG_NO_FUSE)) \
+            and not exhaustive and not profile and r_offset == 0:
+        if isinstance(filter_copy, FilterCopy):
+            fc = filter_copy
+        elif filter_copy == "auto":
+            fc = _filter_copy_auto(ds) if _filter_copy_enabled() else None
+        else:
+            raise ValueError('filter_copy must be "auto", None or a FilterCopy')
+    args = (dev.index, _stream_ptr(dev), ds.data_ptr(), R, T, r_offset, q.data_ptr(),
             None if qnorm is None else qnorm.data_ptr(), B, W, h, k,
             out_d.data_ptr(), out_idx.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
             C.byref(prof) if prof is not None else None)
-    _check(rc, "psh_scan_topk_exhaustive" if exhaustive else "psh_scan_topk")
+    if fc is not None:
+        fc.use(torch.cuda.current_stream(dev))
+        _check(load().psh_scan_topk_copy(*args, C.byref(fc.desc)), "psh_scan_topk_copy")
+    else:
+        fn = load().psh_scan_topk_exhaustive if exhaustive else load().psh_scan_topk
+        _check(fn(*args), "psh_scan_topk_exhaustive" if exhaustive else "psh_scan_topk")
     if info is not None:
-        info.update(path=prof.path, n_sample_rows=prof.n_sample_rows, grid_blocks=prof.grid_blocks)
+        info.update(path=prof.path, n_sample_rows=prof.n_sample_rows, grid_blocks=prof.grid_blocks,
+                    copy_served=0 if fc is None else fc.desc.served, copy_reason=None if fc is None else fc.desc.reason)
     if profile:
         return out_d, out_idx, status, prof.as_dict()
     return out_d, out_idx, status
@@ -367,6 +503,7 @@ def scan_topk_checked(dataset: torch.Tensor, queries: torch.Tensor, k: int, h: i
         st = status.cpu()
     if bool((st == PSH_STATUS_RETRY).any()):
         ws.arm()
+        filter_copy_forget(dataset)        # (the copy scan's audit raises RETRY too: a copy that may be stale is not kept)
         d, idx, status = scan_topk(dataset, queries, k, h=h, r_offset=r_offset, workspace=ws, out=out, unsorted=unsorted,
                                    flags=(flags & ~FLAG_OVERLAP) | FLAG_NO_FUSE)
         st = status.cpu()
@@ -556,8 +693,10 @@ class PreparedShadow:
     out again only after the previous call's results have been taken."""
 
     def __init__(self, rows: torch.Tensor, ds3: torch.Tensor, W: int, k: int, h: int, workspace: "Workspace", flags: int,
-                 host_direct: bool = False):
-        """`host_direct`: the kernels read the query from the pinned staging buffer and write their results into the pinned
+                 host_direct: bool = False, filter_copy: "FilterCopy | None" = None):
+        """`filter_copy`: a FilterCopy of `rows` the owner keeps for its resident ensemble: the scan goes through
+        psh_scan_topk_copy (the copy serves the overlap launches of a query with W <= 33; any other call is psh_scan_topk's).
+        `host_direct`: the kernels read the query from the pinned staging buffer and write their results into the pinned
         result buffer themselves (host memory mapped into the device's address space: ~170 KB over PCIe as posted writes) --
         no copy engine in the chain of a BLOCKING call, whose latency is what counts."""
         self.host_direct = host_direct
@@ -604,6 +743,13 @@ class PreparedShadow:
         self._scan_fn, self._gather_fn = L.psh_scan_topk, L.psh_gather_paths
         self._scan_args = [dev.index, None, rows.data_ptr(), R, T, 0, self.q_dev.data_ptr(), None, 1, W, h, k, self.d.data_ptr(),
                            self.idx.data_ptr(), self.status.data_ptr(), ws.data_ptr(), ws.numel(), C.byref(self.prof)]
+        self.filter_copy = filter_copy
+        if filter_copy is not None:
+            if (filter_copy.R, filter_copy.T) != (R, T):
+                raise ValueError("filter_copy was built from an ensemble of another shape")
+            self._fc_desc = PshFilterCopy(filter_copy.buf.data_ptr(), filter_copy.pitch_halves, R, T, 0, 0)   # (served / reason: this slot's)
+            self._scan_fn = L.psh_scan_topk_copy
+            self._scan_args.append(C.byref(self._fc_desc))
         self._gather_args = [dev.index, None, ds3.data_ptr(), ds3.shape[0], C_, ds3.shape[2], 0, self.idx.data_ptr(), k, W + h,
                              self.paths.data_ptr()]
 
@@ -641,6 +787,8 @@ class PreparedShadow:
             self._stage_np[self._Wp] = hint
         self.prof.tau_hint = self._hint_ptr if hint is not None else None
         sp = stream.cuda_stream
+        if self.filter_copy is not None:
+            self.filter_copy.use(stream)
         if self.host_direct:
             # nothing here is a torch operation: the kernels read the pinned staging buffer and write the pinned result buffer
             # themselves -- two library calls and the event, no stream context to enter and leave (5 us of a blocking call)

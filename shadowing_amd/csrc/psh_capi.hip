@@ -287,6 +287,7 @@ struct Call {
     int flags;            // psh_profile.flags (0 without a profile)
     bool stages, events;  // PSH_PROFILE_STAGES; PSH_PROFILE_EVENTS with both events given
     int ncu; Tuning tn;
+    psh_filter_copy* fc;  // psh_scan_topk_copy: the resident f16 copy of `dataset` (nullable)
 };
 Call make_call(int device, void* stream, const float* dataset, const float* queries, const float* qnorm,
                float* out_d, int32_t* out_idx, int32_t* out_status, psh_profile* prof) {
@@ -834,12 +835,30 @@ static int try_stream_step(const Call& c, const Problem& p, const Workspace& w, 
     fu.cand_cap = cand_cap;
     fu.cand_list = cand_list;
     fu.k_out = p.k;
+    // the caller's resident f16 copy serves ONE route: one query, W <= 33, PSH_FLAG_OVERLAP (with a tau_hint or without: the sample
+    // launch's last block derives the step's scale either way) -- and only a copy of this shape
+    CopyArgs cp{nullptr, nullptr, 0};
+    if (c.fc) {
+        c.fc->served = 0;
+        if (!(one_overlap && !one_long)) c.fc->reason = PSH_COPY_NOT_ROUTE;
+        else if (!(c.fc->copy && c.fc->R == p.R && c.fc->T == p.T && c.fc->pitch_halves == filter_copy_pitch(p.T) && p.r_offset + p.R < (1ll << 31) &&
+                   ((uintptr_t)c.fc->copy & 15) == 0))
+            c.fc->reason = PSH_COPY_MISMATCH;
+        else {
+            cp.hdr = reinterpret_cast<const CopyHdr*>(c.fc->copy);
+            cp.rows = reinterpret_cast<const unsigned short*>(cp.hdr + 1);
+            cp.pitch = c.fc->pitch_halves;
+            fu.copy_ec = &cp.hdr->e_c;
+        }
+    }
     if (rt.hint) grid_p = 1;                  // nothing is sampled: one block derives scale, thresholds and the fragment table from the hints
     if (!(tn.stream_skip & 1)) HIP_TRY(long_mx_sample ? launch_stream_sample_long(fa, fu, (int)grid_p, c.s)
                                                       : launch_stream_sample(fa, fu, p.aligned, (int)grid_p, tile_floats_for(p.W), c.s));
     if (c.events) HIP_TRY(hipEventRecord((hipEvent_t)c.profile->ev_scan_begin, c.s));
-    if (!(tn.stream_skip & 4)) HIP_TRY(one_long ? launch_stream_scan_long(fa, fu, p.aligned, (int)grid_s, c.s)
-                                                : launch_stream_scan(fa, fu, p.aligned, (int)grid_s, c.s));
+    if (!(tn.stream_skip & 4)) HIP_TRY(cp.hdr ? launch_copy_scan(fa, fu, cp, (int)grid_s, c.s)
+                                       : one_long ? launch_stream_scan_long(fa, fu, p.aligned, (int)grid_s, c.s)
+                                                  : launch_stream_scan(fa, fu, p.aligned, (int)grid_s, c.s));
+    if (cp.hdr) { c.fc->served = 1; c.fc->reason = PSH_COPY_SERVED; }
     if (c.events) HIP_TRY(hipEventRecord((hipEvent_t)c.profile->ev_scan_end, c.s));
     // (~2.5 k candidates per query: <= 8 own ones per wave, ONE pass over all of them)
     if (!(tn.stream_skip & 2)) HIP_TRY(launch_stream_rank(fa, fu, tn.stream_rgrid_per_cu * c.ncu, c.s));
@@ -1154,6 +1173,39 @@ int psh_scan_topk(int device, void* stream, const float* dataset, int64_t R, int
                   void* workspace, size_t workspace_bytes, psh_profile* profile) {
     return scan_topk_impl(make_call(device, stream, dataset, queries, qnorm, out_d, out_idx, out_status, profile),
                           R, T, r_offset, B, W, h, k, nullptr, 0, workspace, workspace_bytes);
+}
+
+int psh_filter_copy_bytes(int64_t R, int64_t T, size_t* bytes, int64_t* pitch_halves) {
+    if (!bytes || !pitch_halves || R <= 0 || T <= 0) return PSH_ERR_ARG;
+    if (T >= (1ll << 31) - PSH_SEG - 1024 || R >= (1ll << 31)) return PSH_ERR_UNSUPPORTED;
+    const int64_t pitch = filter_copy_pitch(T);
+    *pitch_halves = pitch;
+    *bytes = sizeof(CopyHdr) + (size_t)R * (size_t)pitch * 2;
+    return PSH_OK;
+}
+
+int psh_filter_copy_build(int device, void* stream, const float* dataset, int64_t R, int64_t T, void* out, size_t out_bytes,
+                          void* scratch, size_t scratch_bytes) {
+    size_t need = 0;
+    int64_t pitch = 0;
+    if (!dataset || !out || !scratch) return PSH_ERR_ARG;
+    const int rc = psh_filter_copy_bytes(R, T, &need, &pitch); if (rc) return rc;
+    if (out_bytes < need || scratch_bytes < PSH_FILTER_COPY_SCRATCH_BYTES) return PSH_ERR_WORKSPACE;
+    if (((uintptr_t)out & 15) || ((uintptr_t)scratch & 7)) return PSH_ERR_ARG;
+    GUARD_DEVICE(device);
+    HIP_TRY(launch_filter_copy_build(dataset, R, T, out, scratch, (hipStream_t)stream));
+    return PSH_OK;
+}
+
+int psh_scan_topk_copy(int device, void* stream, const float* dataset, int64_t R, int64_t T, int64_t r_offset,
+                       const float* queries, const float* qnorm, int B, int W, int h, int k,
+                       float* out_d, int32_t* out_idx, int32_t* out_status,
+                       void* workspace, size_t workspace_bytes, psh_profile* profile, psh_filter_copy* copy) {
+    Call c = make_call(device, stream, dataset, queries, qnorm, out_d, out_idx, out_status, profile);
+    c.fc = copy;
+    // (every route but the one the copy serves leaves these as they are: the call went the ordinary way)
+    if (copy) { copy->served = 0; copy->reason = PSH_COPY_NOT_ROUTE; }
+    return scan_topk_impl(c, R, T, r_offset, B, W, h, k, nullptr, 0, workspace, workspace_bytes);
 }
 
 int psh_scan_topk_embedded(int device, void* stream, const float* dataset, int64_t R, int64_t T, int64_t r_offset,

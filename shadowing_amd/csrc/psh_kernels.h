@@ -118,6 +118,8 @@ struct FusedArgs {
     unsigned* done;                  // nullable: done_shards device-addressable words; shard i's last block stores done_val there
     unsigned done_val;
     int done_shards;                 //   blocks are dealt to the shards round-robin (blockIdx % done_shards): one counter each in FusedHdr::pad
+    const int* copy_ec;              // nullable: the exponent e_c in the header of a resident f16 filter copy (psh_stream_copy.hip): the
+                                     //   step's f16 scale is then at most 2^e_c and its threshold takes the copy route's constants
 };
 #define PSH_FUSED_DONE_SHARDS 8      // completion counters of a blocking call: FusedHdr::pad[4 .. 11]
 
@@ -338,6 +340,27 @@ size_t stream_scan_shmem_bytes_q(int tile_floats, int nq);
 bool stream_long_supported(int W);              // one to three queries, 34 <= W <= 256: the scan of the step as a K-loop over the band (stream_scan_long_kernel)
 size_t stream_scan_long_shmem_bytes(int W, int nq);
 hipError_t launch_stream_scan_long(const ScanArgs& a, const FusedArgs& f, bool aligned, int grid, hipStream_t s);
+// psh_stream_copy.hip: a resident f16 copy of the ensemble (64-byte header, then R rows of `pitch` halves) and the one-query
+// scan of the three launches that streams it instead of the fp32 samples
+#define PSH_COPY_MAGIC 0x43485350u   // "PSHC"
+struct CopyHdr {                     // written by the build's second launch, read by the sample and the scan: never by the host
+    unsigned magic;
+    int e_c;                         // the copy holds (f16)(y 2^e_c)
+    long long R, T, pitch;
+    unsigned pad[8];
+};
+static_assert(sizeof(CopyHdr) == 64, "the rows start 64 bytes into the copy");
+struct CopyArgs {
+    const CopyHdr* hdr;
+    const unsigned short* rows;      // row r: rows + r * pitch, `pitch` halves (a multiple of 8)
+    long long pitch;
+};
+// a row's halves: every segment start s * PSH_SEG <= T - 1 may be followed by PSH_SEG + 32 halves inside the row
+__host__ __device__ inline long long filter_copy_pitch(long long T) { return (T + PSH_SEG - 1) / PSH_SEG * PSH_SEG + 32; }
+#define PSH_COPY_BUILD_BLOCKS 1024   // partial sums of the build's first pass (a double and a count each in the scratch)
+hipError_t launch_filter_copy_build(const float* ds, long long R, long long T, void* out, void* scratch, hipStream_t s);
+size_t copy_scan_shmem_bytes(int tile_floats);
+hipError_t launch_copy_scan(const ScanArgs& a, const FusedArgs& f, const CopyArgs& cp, int grid, hipStream_t s);
 // psh_lq.hip: batched queries with a long window (B >= 4, 34 <= W <= 256): BOOT / FILTER of the separate launches' pipeline
 // the batched long-window scan's layout of a query's B fragments (psh_lq.hip), shared with the long-window sample (psh_stream.hip)
 __host__ __device__ inline int lq_ksteps(int W) { return (W + 31 + 15) / 16; }

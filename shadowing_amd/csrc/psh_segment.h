@@ -263,4 +263,18 @@ __device__ __forceinline__ void mx_admit(const f32x16& acc, float thr, float tau
     }
 }
 
+// A block's list of admitted windows is full (clustered matches: a smooth ensemble -- price levels, not returns -- puts a
+// window's neighbours in t next to it in distance too): the entry goes straight to the query's compact list in memory, one
+// device-scope atomic per entry (r05; until then such a step gave up -- PSH_STATUS_RETRY -- and the caller ran the separate launches)
+__device__ __forceinline__ void spill_candidate(FusedHdr* hdr, void* cand_list, int cand_cap, int q, float xn, float acc, int r_global, int t) {
+    const unsigned slot = __hip_atomic_fetch_add((gu32*)&hdr->stream.ncand[q], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (slot < (unsigned)cand_cap)
+        reinterpret_cast<u32x4*>(cand_list)[(size_t)q * cand_cap + slot] = u32x4{__float_as_uint(dist_from_acc(acc, xn)), (unsigned)r_global, (unsigned)t, (unsigned)q};
+}
+
+// the rejection threshold's constants when the scan streams the resident f16 copy (derivation: psh_stream_copy.hip, above
+// copy_scan_kernel): relative part a, absolute part b (up to W = 31; (2 W + 2) / 64 of it beyond, as on the fp32 route)
+#define PSH_COPY_A (1.0 / 320.0)
+#define PSH_COPY_B (1.0 / 131072.0)
+
 }  // namespace psh

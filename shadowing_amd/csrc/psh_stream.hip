@@ -61,22 +61,24 @@ __device__ inline bool stream_sexp_of(unsigned qmaxbits, float tau0, int* sexp_o
     *sexp_out = sexp;
     return true;
 }
-__device__ inline bool stream_threshold_of(double nxs, int W, float tau0, float sc, float* thr_out);
-__device__ inline bool stream_threshold(const_f32p xq, int W, float tau0, float sc, float* thr_out) {
+__device__ inline bool stream_threshold_of(double nxs, int W, float tau0, float sc, float* thr_out, bool copy = false);
+__device__ inline bool stream_threshold(const_f32p xq, int W, float tau0, float sc, float* thr_out, bool copy = false) {
     double nxs = 0.0;
 #pragma unroll 1
     for (int j = 0; j < W; ++j) { const double vv = (double)xq[j] * (double)sc; nxs += vv * vv; }
-    return stream_threshold_of(nxs, W, tau0, sc, thr_out);
+    return stream_threshold_of(nxs, W, tau0, sc, thr_out, copy);
 }
-// (nxs: the sum of (x_j sc)^2 in double)
-__device__ inline bool stream_threshold_of(double nxs, int W, float tau0, float sc, float* thr_out) {
+// (nxs: the sum of (x_j sc)^2 in double; copy: the scan streams the resident f16 copy -- its own constant pair, derived above
+//  copy_scan_kernel in psh_stream_copy.hip)
+__device__ inline bool stream_threshold_of(double nxs, int W, float tau0, float sc, float* thr_out, bool copy) {
     // (b: the absolute part of the bound -- f16 subnormals, one unit of 2^-24 per product -- grows with the taps: 2^-18 covers the
     //  2 W + 1 = 41 .. 67 terms of W <= 33; a long window takes (2 W + 2) / 64 of it)
     // a: the relative part.  W <= 33: 2^-9 covers the f16 roundings of x~, y~ AND (y~^2)^ plus the fp32 accumulation of both banded
     // products.  A long window's energies are fp32 prefix sums whose error the tile's C operand takes off separately (round 6:
     // ce <= E by construction), so only the correlation is left:  |c^ - c| <= (2^-10 (1 + 2^-12) + 2 x 288 x 2^-24)(nx~ + E) / 2 x 2,
     // and with E <= 2 (nx~ + acc~):  t^ <= acc~ (1 + 2 a') - nx~ (1 - 3 a'),  a' = 1.012e-3 -> 1 / 900 with a tenth to spare.
-    const double am = W > 33 ? 1.0 / 900.0 : 1.0 / 512.0, bm = (1.0 / 262144.0) * (W > 31 ? (double)(2 * W + 2) / 64.0 : 1.0);
+    const double am = copy ? PSH_COPY_A : (W > 33 ? 1.0 / 900.0 : 1.0 / 512.0);
+    const double bm = (copy ? PSH_COPY_B : 1.0 / 262144.0) * (W > 31 ? (double)(2 * W + 2) / 64.0 : 1.0);
     const double taus = (double)tau0 * (double)sc * (double)sc;
     const double T = taus * (1.0 + 1.0 / 131072.0) * (1.0 + 2.0 * am) - nxs * (1.0 - 3.0 * am) * (1.0 - 1e-12) + bm;
     float Tf = (float)T;
@@ -226,6 +228,17 @@ __device__ __forceinline__ void stream_sample_finish(const ScanArgs& a, const Fu
     bool armed = true;
     int sexp_common = 1000;
     for (int q = 0; q < nq; ++q) { armed = armed && sh_armed[q] != 0; sexp_common = sh_sexp[q] < sexp_common ? sh_sexp[q] : sexp_common; }
+    // the scan streams a resident f16 copy (y 2^e_c)^ (psh_stream_copy.hip): it can scale those values DOWN by a power of two (exact
+    // but for subnormals), never up -- the step's exponent is at most e_c.  A query whose proof wants less than e_c - 14 (2^14 times
+    // louder than the ensemble: every window is about as far as ||x||) leaves the copy nothing but subnormals: no window is rejected
+    bool copy_flood = false;
+    if (f.copy_ec) {
+        int ec = *f.copy_ec;
+        ec = ec < -60 ? -60 : (ec > 60 ? 60 : ec);
+        copy_flood = sexp_common < ec - 14;
+        sexp_common = ec < sexp_common ? ec : sexp_common;
+    }
+    const bool copy = f.copy_ec != nullptr;
     const float scale = armed ? __uint_as_float((unsigned)(127 + sexp_common) << 23) : 0.0f;
 #pragma unroll 1
     for (int q = (NWP == 1 ? 0 : wave); q < nq; q += NWP) {
@@ -239,8 +252,9 @@ __device__ __forceinline__ void stream_sample_finish(const ScanArgs& a, const Fu
             for (int j = lane; j < W; j += 64) { const double vv = (double)xs[(size_t)q * W + j] * (double)scale; part += vv * vv; }
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
-            if (!stream_threshold_of(part, W, tau0q_, scale, &thr)) sh_armed[q] = 0;
-        } else if (armed && !stream_threshold(xq, W, tau0q_, scale, &thr)) sh_armed[q] = 0;
+            if (!stream_threshold_of(part, W, tau0q_, scale, &thr, copy)) sh_armed[q] = 0;
+        } else if (armed && !stream_threshold(xq, W, tau0q_, scale, &thr, copy)) sh_armed[q] = 0;
+        if (copy_flood) thr = __uint_as_float(PSH_INF_BITS);
         if (lane == 0) {
             // (||x||: the reference's order -- sumsq8 --, from the staged copy when there is one)
             const float s2 = xs ? sumsq8([&](int j) { return xs[(size_t)q * W + j]; }, W) : sumsq8([&](int j) { return xq[j]; }, W);
@@ -346,14 +360,7 @@ void stream_sample_kernel(ScanArgs a, FusedArgs f) {
 // S: the scan
 // ------------------------------------------------------------------------------------------------------------------
 #define PSH_STREAM_FIXED_BYTES 256    // control words; the block's candidate list follows
-// A block's list of admitted windows is full (clustered matches: a smooth ensemble -- price levels, not returns -- puts a
-// window's neighbours in t next to it in distance too): the entry goes straight to the query's compact list in memory, one
-// device-scope atomic per entry (r05; until then such a step gave up -- PSH_STATUS_RETRY -- and the caller ran the separate launches)
-__device__ __forceinline__ void spill_candidate(FusedHdr* hdr, void* cand_list, int cand_cap, int q, float xn, float acc, int r_global, int t) {
-    const unsigned slot = __hip_atomic_fetch_add((gu32*)&hdr->stream.ncand[q], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (slot < (unsigned)cand_cap)
-        reinterpret_cast<u32x4*>(cand_list)[(size_t)q * cand_cap + slot] = u32x4{__float_as_uint(dist_from_acc(acc, xn)), (unsigned)r_global, (unsigned)t, (unsigned)q};
-}
+// (spill_candidate -- a block's list of admitted windows is full -- : psh_segment.h, shared with psh_stream_copy.hip)
 #define PSH_STREAM_FL(NQ) ((NQ) == 1 ? PSH_FUSED_FRONT : 2 * PSH_FUSED_FRONT)
 enum { S_FRONT = 0, S_NEXT = 1 };
 

@@ -183,6 +183,7 @@ class PathShadowing:
         """Forget the copy of `dataset` resident in HBM: call after editing the array in place when the object
         was built with cache=True (with cache="auto" a writeable numpy array is re-read on every call anyway)."""
         self._resident = self._scan_rows = self._dirty_split = None
+        self._async = None       # (shadow_async's prepared slots and their f16 filter copy: a new upload may land at the old address)
         self._gen += 1
 
     def _may_keep_resident(self) -> bool:
@@ -775,6 +776,10 @@ class PathShadowing:
             for s_ in st["streams"]:
                 s_.wait_stream(cur)                                   # (the resident ensemble may just have been uploaded there)
             st["slots"] = [[] for _ in range(n)]
+            # one f16 filter copy per resident ensemble (psh_filter_copy_build on the current stream; the slots' streams wait
+            # for its event): the overlap scans of a query with W <= 33 stream it instead of the fp32 samples.  It lives and
+            # dies with this state -- the key above holds the ensemble's version counter
+            st["copy"] = self._build_filter_copy(rows, W)
         i = st["i"] % st["n"]
         st["i"] += 1
         # a free slot of this stream, or a new one (a slot is busy until its handle's result() has been taken)
@@ -782,13 +787,24 @@ class PathShadowing:
         slot = next((sl for sl in pool if not sl.busy), None)
         if slot is None:
             with torch.cuda.stream(st["streams"][i]):
-                slot = _native.PreparedShadow(rows, ds, W, k, h, st["ws"][i], _native.FLAG_OVERLAP)
+                slot = _native.PreparedShadow(rows, ds, W, k, h, st["ws"][i], _native.FLAG_OVERLAP, filter_copy=st["copy"])
             slot.busy = False
             pool.append(slot)
         slot.busy = True
         slot.launch(st["streams"][i], x[:, 0, :])
         self.last_path = "hip"
         return PendingShadow(self, slot.event, slot, (x_context, k))
+
+    @staticmethod
+    def _build_filter_copy(rows, W: int):
+        """The FilterCopy shadow_async keeps for its resident ensemble, or None: switched off (_native.FILTER_COPY_POLICY,
+        PSH_FILTER_COPY=0), a window the copy scan does not take, or no room for it and 1 GiB more on the device."""
+        if W > 33 or not _native._filter_copy_enabled():
+            return None
+        nbytes, _ = _native.filter_copy_bytes(rows.shape[0], rows.shape[1])
+        if _native._filter_copy_free_bytes(rows.device) < nbytes + _native._FILTER_COPY_HEADROOM:
+            return None
+        return _native.FilterCopy(rows)
 
     @staticmethod
     def init_averaging_proba(proba_name: str, distances: np.ndarray, eta: float | None) -> DiscreteProba:
@@ -1091,6 +1107,8 @@ class PendingShadow:
             hd, hp, hi, hs = slot.take()                              # (small results: copies; large ones: the pinned buffer itself)
             slot.busy = False
             if hs.any():                                              # the status protocol: rare; the blocking path copes
+                if getattr(slot, "filter_copy", None) is not None:    # (the copy scan's audit may have raised it: the copy goes)
+                    self._owner._async = None
                 x_context, k = self._call
                 hd, hp, hi = self._owner.shadow(x_context, k, cuda=True)
             self._payload, self._call = (hd, hp, hi), None

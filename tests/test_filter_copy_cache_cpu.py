@@ -1,0 +1,129 @@
+"""scan_topk's filter_copy="auto" policy (shadowing_amd/_native.py) with a fake builder: which call builds a copy, what makes
+the policy start over, what drops an entry.  CPU tensors stand in for the ensemble: the policy looks at a tensor's identity,
+pointer, shape, strides, device and version counter, never at its contents."""
+import gc
+
+import pytest
+import torch
+
+from shadowing_amd import _native
+
+
+class Fake:
+    def __init__(self, rows):
+        self.shape = tuple(rows.shape)
+
+
+@pytest.fixture()
+def policy(monkeypatch):
+    built = []
+
+    def builder(rows):
+        built.append(Fake(rows))
+        return built[-1]
+
+    state = {"capturing": False, "free": 1 << 40}
+    monkeypatch.setattr(_native, "_filter_copy_builder", builder)
+    monkeypatch.setattr(_native, "_filter_copy_capturing", lambda: state["capturing"])
+    monkeypatch.setattr(_native, "_filter_copy_free_bytes", lambda device: state["free"])
+    monkeypatch.setattr(_native, "filter_copy_bytes", lambda R, T: (64 + R * ((T + 1023) // 1024 * 1024 + 32) * 2, 0))
+    monkeypatch.setattr(_native, "FILTER_COPY_POLICY", "second")
+    monkeypatch.delenv("PSH_FILTER_COPY", raising=False)
+    _native._filter_copies.clear()
+    yield built, state
+    _native._filter_copies.clear()
+
+
+def auto(ds):
+    return _native._filter_copy_auto(ds) if _native._filter_copy_enabled() else None
+
+
+def test_the_copy_is_built_on_the_second_consecutive_call(policy):
+    built, _ = policy
+    ds = torch.zeros(64, 2048)
+    assert auto(ds) is None and not built                 # a one-off call pays nothing
+    c = auto(ds)
+    assert c is built[0] and len(built) == 1
+    assert auto(ds) is c and auto(ds) is c and len(built) == 1
+
+
+def test_a_version_bump_starts_over(policy):
+    built, _ = policy
+    ds = torch.zeros(64, 2048)
+    auto(ds); c = auto(ds)
+    ds.add_(1.0)                                           # an in-place edit torch sees
+    assert auto(ds) is None and len(built) == 1            # the stale copy is not handed out, the count starts again
+    c2 = auto(ds)
+    assert c2 is built[1] and c2 is not c
+
+
+def test_views_of_one_base_share_the_entry_and_other_views_do_not(policy):
+    built, _ = policy
+    base = torch.zeros(64, 1, 2048)
+    assert auto(base[:, 0, :]) is None
+    c = auto(base[:, 0, :])                                # a new view object of the same rows each call (bench.py's ds[:, 0, :])
+    assert c is built[0] and auto(base[:, 0, :]) is c
+    assert auto(base[:32, 0, :]) is None                   # other rows of the same base: another key
+    assert len(_native._filter_copies) == 1
+
+
+def test_a_new_tensor_has_its_own_entry(policy):
+    built, _ = policy
+    a, b = torch.zeros(64, 2048), torch.zeros(64, 2048)
+    auto(a); ca = auto(a)
+    assert auto(b) is None
+    cb = auto(b)
+    assert ca is built[0] and cb is built[1] and auto(a) is ca
+
+
+def test_the_entry_dies_with_the_tensor(policy):
+    built, _ = policy
+    ds = torch.zeros(64, 2048)
+    auto(ds); auto(ds)
+    assert len(_native._filter_copies) == 1
+    del ds
+    gc.collect()
+    assert len(_native._filter_copies) == 0
+
+
+def test_forget_drops_the_entry(policy):
+    built, _ = policy
+    base = torch.zeros(64, 1, 2048)
+    auto(base[:, 0, :]); auto(base[:, 0, :])
+    _native.filter_copy_forget(base[:, 0, :])              # (through a view: the entry is the base's)
+    assert len(_native._filter_copies) == 0
+    assert auto(base[:, 0, :]) is None and len(built) == 1
+
+
+def test_policy_and_environment_switches(policy, monkeypatch):
+    built, _ = policy
+    ds = torch.zeros(64, 2048)
+    monkeypatch.setattr(_native, "FILTER_COPY_POLICY", "off")
+    assert auto(ds) is None and auto(ds) is None and auto(ds) is None and not built
+    monkeypatch.setattr(_native, "FILTER_COPY_POLICY", "first")
+    assert auto(ds) is built[0]
+    monkeypatch.setenv("PSH_FILTER_COPY", "0")
+    assert auto(ds) is None and auto(torch.zeros(8, 2048)) is None and len(built) == 1
+    monkeypatch.delenv("PSH_FILTER_COPY")
+    assert auto(ds) is built[0]
+
+
+def test_the_copy_needs_its_bytes_and_a_gibibyte_free(policy):
+    built, state = policy
+    ds = torch.zeros(64, 2048)
+    need = 64 + 64 * (2048 + 32) * 2
+    state["free"] = need + (1 << 30) - 1
+    assert auto(ds) is None and auto(ds) is None and auto(ds) is None and not built
+    ds2 = torch.zeros(64, 2048)
+    state["free"] = need + (1 << 30)
+    auto(ds2)
+    assert auto(ds2) is built[0]
+
+
+def test_nothing_is_built_while_the_stream_captures(policy):
+    built, state = policy
+    ds = torch.zeros(64, 2048)
+    state["capturing"] = True
+    assert auto(ds) is None and auto(ds) is None and auto(ds) is None and not built
+    state["capturing"] = False
+    assert auto(ds) is built[0]                            # the calls were counted: the first one outside a capture builds

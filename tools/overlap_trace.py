@@ -13,8 +13,10 @@ for r in rows:
 for n, v in byname.items():
     d = [e - s for s, e in v]
     print(f"{n:62s} n={len(v):5d} mean {st.mean(d)/1e3:8.2f} us  median {st.median(d)/1e3:8.2f}  min {min(d)/1e3:8.2f}")
-for key in [k for k in byname if "stream_scan" in k or "scan_fused" in k]:
+for key in [k for k in byname if "stream_scan" in k or "scan_fused" in k or "copy_scan" in k]:
     v = byname[key][-200:]
+    if len(v) < 3:                                           # (a kernel launched once or twice: no interval to speak of)
+        continue
     ds = [b[0] - a[0] for a, b in zip(v, v[1:])]
     de = [b[1] - a[1] for a, b in zip(v, v[1:])]
     ov = [a[1] - b[0] for a, b in zip(v, v[1:])]
