@@ -1270,6 +1270,10 @@ __global__ __launch_bounds__(PSH_CHUNK) void chunk_merge_kernel(SelectArgs a) {
 // which IS the (r, t) order because shards are ascending row blocks.  Only entries that can be among
 // the k best take part: with c = ceil(1.25 k / G), everything above P = max_g list_g[c] is out (at
 // least G (c + 1) >= k entries are <= P).  One block per query; the distance keys sit in LDS.
+// Padding takes a key of its own above +inf (PSH_MERGE_PAD_KEY), or the padding of a lower list would
+// precede a REAL entry at +inf of a higher one (equal keys: the lower list first); only entries at
+// +inf have their r read for this.
+#define PSH_MERGE_PAD_KEY 0xffffffffu
 __global__ __launch_bounds__(PSH_SELECT_THREADS) void merge_sorted_kernel(MergeSortedArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned mkeys[];     // G x k_in distance bits (non-negative floats: bit order)
     __shared__ int ncut[64];                                              // per list: entries <= P
@@ -1278,7 +1282,9 @@ __global__ __launch_bounds__(PSH_SELECT_THREADS) void merge_sorted_kernel(MergeS
     const int G = a.G, kin = a.k_in;
     for (int e = tid; e < G * kin; e += PSH_SELECT_THREADS) {
         const int g = e / kin, j = e - g * kin;
-        mkeys[e] = __float_as_uint(a.d[(int64_t)g * a.stride_d + (int64_t)b * kin + j]);
+        unsigned key = __float_as_uint(a.d[(int64_t)g * a.stride_d + (int64_t)b * kin + j]);
+        if (key == PSH_INF_BITS && a.rt[(int64_t)g * a.stride_rt + (int64_t)b * kin + j].x < 0) key = PSH_MERGE_PAD_KEY;
+        mkeys[e] = key;
     }
     if (tid == 0) pivot = 0u;
     __syncthreads();
@@ -1312,7 +1318,7 @@ __global__ __launch_bounds__(PSH_SELECT_THREADS) void merge_sorted_kernel(MergeS
         }
         if (rank < a.k) {
             const int2 rt = a.rt[(int64_t)g * a.stride_rt + (int64_t)b * kin + j];
-            a.out_d[(int64_t)b * a.k + rank] = __uint_as_float(mine);
+            a.out_d[(int64_t)b * a.k + rank] = __uint_as_float(mine == PSH_MERGE_PAD_KEY ? PSH_INF_BITS : mine);
             a.out_idx[((int64_t)b * a.k + rank) * 2 + 0] = rt.x;
             a.out_idx[((int64_t)b * a.k + rank) * 2 + 1] = rt.y;
         }

@@ -165,3 +165,47 @@ def test_an_ensemble_made_on_the_device_is_measured_where_it_lies_and_fitted(mon
         assert fit[name] == pytest.approx(host[name], rel=1e-9)
     again = sa.smrw_log_returns(4, n, cuda=True, seed=3, **{k: fit["params"][k] for k in ("K0", "alpha", "lam", "sigma")})
     assert again.is_cuda and again.shape == (4, 1, n)
+
+
+# ---- integer ensembles: the device equals an int64 reference exactly, on every plan of moments_lag_plan ----
+import _moments_exact as mx                                                     # noqa: E402
+
+
+def _device_sums(x, m, G):
+    d_sums, d_rows, status = _native.lagged_moments(torch.from_numpy(np.ascontiguousarray(x)).cuda(), m, G)
+    assert int(status.item()) == 0
+    return d_sums.cpu().numpy(), d_rows.cpu().numpy()
+
+
+@pytest.mark.parametrize("shape", mx.census_shapes(), ids=mx.census_id)
+def test_device_equals_the_int64_reference_on_every_plan(shape):
+    """The plan census of tests/_moments_exact.py: every (U, C, S), both sides of each boundary of m, a second tile of
+    m + 3 samples behind a full one and a single tile of m + 1.  Integer samples: == , no tolerance."""
+    R, n, m, G = shape
+    x = mx.int_ensemble(R, n, 7)
+    s, rows = _device_sums(x, m, G)
+    assert s.shape == (G, 4, m + 1) and np.array_equal(s, mx.int_sums(x, m, G).astype(np.float64))
+    assert np.array_equal(rows, np.diff(stylized.group_bounds(R, G))) and np.array_equal(s[:, 1, 0], s[:, 2, 0])
+
+
+@pytest.mark.parametrize("m", mx.PLANT_M, ids=[f"m{m}-U{mx.lag_plan(m)[0]}C{mx.lag_plan(m)[1]}S{mx.lag_plan(m)[2]}" for m in mx.PLANT_M])
+def test_device_finds_every_impulse_plant_exactly(m):
+    """One pair a row (2 at t1, 3 at t1 + tau) at the row's ends, across the tile boundary from both sides, in the ragged
+    last tile and on both sides of every slice boundary of the first tile: (6, 18, 12, 36) at lag tau, (13, 35, 35, 97) at
+    lag 0 and 0 at every other lag.  A failure names the plants."""
+    x, want = mx.plants(m)
+    s, rows = _device_sums(x, m, len(x))
+    bad = [mx.plant_positions(m)[i] for i in np.flatnonzero((s != want.astype(np.float64)).any(axis=(1, 2)))]
+    assert not bad, f"plants (t1, tau) with wrong sums: {bad}"
+    assert np.array_equal(rows, np.ones(len(x), np.int64))
+
+
+def test_partition_invariance_is_exact_on_integers_on_the_device():
+    """37 rows x 300 at m = 70: the sums added over the groups are bit-identical for 1, 2, 5 and 37 groups (2 and 5:
+    groups of unequal size, and units that hold no row)."""
+    x = mx.int_ensemble(37, 300, 11)
+    total = mx.int_sums(x, 70, 1)[0].astype(np.float64)
+    for G in (1, 2, 5, 37):
+        s, rows = _device_sums(x, 70, G)
+        assert np.array_equal(s, mx.int_sums(x, 70, G).astype(np.float64)), G
+        assert np.array_equal(s.sum(axis=0), total) and np.array_equal(rows, np.diff(stylized.group_bounds(37, G)))

@@ -215,3 +215,65 @@ def test_the_public_names():
         assert getattr(shadowing, name) is getattr(sa, name) and name in sa.__all__
     assert sa.lagged_moments is stylized.lagged_moments and sa.fit_smrw is stylized.fit_smrw
     assert sa.LaggedMoments is stylized.LaggedMoments and sa.smrw_sq_moment is mrw.smrw_sq_moment
+
+
+# ---- integer ensembles: the twin equals an int64 reference exactly, on every plan of the device's kernel ----
+import _moments_exact as mx                                                     # noqa: E402
+
+
+def test_the_plan_helper_covers_every_plan_and_both_sides_of_every_boundary():
+    plans = {m: mx.lag_plan(m) for m in mx.CENSUS_M}
+    assert {p[0] for p in plans.values()} == {1, 2, 4} and {p[1] for p in plans.values()} == {1, 2, 3, 4}
+    for lo, hi in mx.BOUNDARIES:
+        assert lo in plans and hi in plans and plans[lo] != plans[hi] and mx.lag_plan(lo + 1) == plans[hi]
+    assert [mx.lag_plan(m) for m in (1, 64, 65, 128, 129, 256, 257, 512, 513, 768, 769, 1024)] == [
+        (1, 1, 8), (1, 1, 8), (2, 1, 8), (2, 1, 8), (4, 1, 8), (4, 1, 8), (4, 2, 4), (4, 2, 4), (4, 3, 2), (4, 3, 2), (4, 4, 2), (4, 4, 2)]
+    assert {mx.lag_plan(m)[:2] for m in mx.CENSUS_M} == {mx.lag_plan(m)[:2] for m in range(1, 1025)}       # all six (U, C)
+    assert {mx.lag_plan(m)[:2] for m in mx.PLANT_M} == {mx.lag_plan(m)[:2] for m in range(1, 1025)}
+    assert mx.lag_plan(600)[1] * mx.lag_plan(600)[2] == 6 < mx.WAVES           # C = 3: waves 6 and 7 are not workers
+    assert [mx.slice_len(m) for m in mx.PLANT_M] == [256, 256, 256, 512, 1024, 1024]
+    for R, n, m, G in mx.census_shapes():
+        assert m < n and n - mx.LT in (m + 3, m + 1 - mx.LT)
+    # the second tile's m + 3 samples are no multiple of U = 4 (the staging rounds them up) except where m = 1 mod 4
+    assert {m for m in mx.CENSUS_M if m > 128 and (m + 3) % 4 == 0} == {129, 257, 513, 769}
+
+
+@pytest.mark.parametrize("shape", mx.census_shapes(), ids=mx.census_id)
+def test_twin_equals_the_int64_reference_on_integer_samples(shape):
+    R, n, m, G = shape
+    x = mx.int_ensemble(R, n, 7)
+    sums, rows = stylized._host_sums(x, m, G)
+    want = mx.int_sums(x, m, G)
+    assert np.abs(want).max() < 2 ** 40 and np.array_equal(sums, want.astype(np.float64))
+    assert np.array_equal(rows, np.diff(stylized.group_bounds(R, G))) and np.array_equal(sums[:, 1, 0], sums[:, 2, 0])
+    assert np.any(want[:, :, m] != 0)                                            # the largest lag is not trivially zero
+
+
+@pytest.mark.parametrize("m", mx.PLANT_M)
+def test_twin_finds_every_impulse_plant_exactly(m):
+    x, want = mx.plants(m)
+    assert len(x) == 7 + 4 * (mx.lag_plan(m)[2] - 1)
+    sums, rows = stylized._host_sums(x, m, len(x))
+    assert np.array_equal(sums, want.astype(np.float64)) and np.array_equal(rows, np.ones(len(x), np.int64))
+    assert np.array_equal(mx.int_sums(x, m, len(x)), want)
+
+
+def test_one_dropped_pair_is_noticed():
+    """A reference that leaves out ONE pair differs from the twin at that (group, lag), in every sum whose summand is
+    not zero there, and nowhere else."""
+    R, n, m, G = 3, mx.LT + 603, 600, 3
+    x = mx.int_ensemble(R, n, 7)
+    sums, _ = stylized._host_sums(x, m, G)
+    for row, tau in ((0, 600), (1, 1), (2, 257)):
+        assert x[row, n - 1 - tau] != 0 and x[row, n - 1] != 0
+        bad = sums != mx.int_sums(x, m, G, drop=(row, tau)).astype(np.float64)
+        assert bad.any() and np.array_equal(np.argwhere(bad)[:, [0, 2]], np.array([[row, tau]] * 4))
+
+
+def test_partition_invariance_is_exact_on_integers():
+    x = mx.int_ensemble(37, 300, 11)
+    total = mx.int_sums(x, 70, 1)[0]
+    for G in (1, 2, 5, 37):
+        sums, rows = stylized._host_sums(x, 70, G)
+        assert np.array_equal(sums, mx.int_sums(x, 70, G).astype(np.float64))
+        assert np.array_equal(sums.sum(axis=0), total.astype(np.float64)) and rows.sum() == 37
