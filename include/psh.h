@@ -604,6 +604,46 @@ int psh_hedged_mc(int device, void* stream, const float* dlnx, int64_t row_strid
                   int32_t* out_status);
 
 /*
+ * The hedge of a smile: the fit of psh_hedged_mc with its policy kept, and the replay of a policy on paths.  The
+ * definition, in full, heads shadowing_amd/csrc/psh_hmc_report.hip (and README "Option pricing"); pricing.py
+ * (replay_host) is the numpy twin.
+ *   The policy of one (date b, maturity q, strike j) holds, for every step n < Ts[q], mu_n, isd_n (the standardisation of
+ *   S_n), gamma_n[0..P] and beta_n[0..P] of the fit (P = degree; dropped unknowns are 0), double, row-major:
+ *     policy[b][q][j][n][c],  n < Tmax = max Ts,  c < 2P + 4 = [mu, isd, gamma_0..P, beta_0..P];  rows n >= Ts[q] are 0.
+ *   delta = beta_0[0] = policy[b][q][j][0][P + 3], the hedge ratio at inception.
+ *   psh_hmc_policy_doubles: the doubles of a policy, B * nT * nM * Tmax * (2 degree + 4) (host only).
+ *   psh_hedged_mc_policy: psh_hedged_mc -- the same arguments, the same five outputs bit for bit -- and out_policy.
+ *   psh_hedge_replay: on B x k paths (any k; dlnx, row_stride, len, weights as psh_hedged_mc) with the policy, `strike` and
+ *   `centre` (device B x nT x nM: the FIT's out_strike and out_price) and the fit's x_init, rate, Ts, Ms, degree, kind:
+ *     l_0 = 0, l_{n+1} = l_n + r[i, n];  S_n = x_init exp(l_n), S_0 = x_init;  u_n = (S_n - mu_n) isd_n;
+ *     phi_n = sum_a beta_n[a] u_n^a (Horner);  D_n = e^-rho S_{n+1} - S_n, rho = rate / 252;
+ *     gain_i = sum_{n<T} exp(-rho n) phi_n D_n;  pay_i = exp(-rho T) payoff_j(S_T);  pnl_i = pay_i - gain_i;
+ *   out_sums: device B x nT x nM x 9 float64, with c = centre and w the weights normalised by their sum:
+ *     [a1 = sum w (pnl - c), a2 = sum w (pnl - c)^2, b1 = sum w^2 (pnl - c), b2 = sum w^2 (pnl - c)^2,
+ *      p1, p2, q1, q2: the same four of pay, s2 = sum w^2]:
+ *     mean = c + a1, risk = sqrt(max(a2 - a1^2, 0)), se = sqrt(max(b2 - 2 a1 b1 + a1^2 s2, 0)), mc = c + p1,
+ *     risk_unhedged and se_unhedged likewise from p and q, n_eff = 1 / s2.  se treats the policy as fixed: honest on
+ *     paths the policy was not fitted on, optimistic on the fit's own.
+ *   out_pnl: device B x nT x nM x k float64 or NULL (a path of weight 0: NaN);
+ *   out_status: device B int32 or NULL (NONFINITE / WEIGHTS as psh_hedged_mc: all the date's sums and pnl are NaN);
+ *   a centre that is not finite (a maturity the fit flagged): NaN sums and pnl there;
+ *   workspace: device, psh_hedge_replay_workspace_bytes(B, k, nT, nM) bytes (PSH_ERR_WORKSPACE when smaller).
+ * degree > 5, or max Ts beyond what the policy rows of a strike group fit in LDS (833 at degree 5): PSH_ERR_UNSUPPORTED.
+ * Sums in double, fixed order, no floating-point atomics: two calls give identical bits.
+ */
+int psh_hmc_policy_doubles(int B, int nT, int nM, int Tmax, int degree, size_t* out);
+int psh_hedged_mc_policy(int device, void* stream, const float* dlnx, int64_t row_stride, int B, int k, int len,
+                         const double* weights, double x_init, double rate, const int* Ts, int nT, const double* Ms, int nM,
+                         int degree, int kind, double* out_price, double* out_iv, double* out_strike, double* out_sigma,
+                         int32_t* out_status, double* out_policy);
+int psh_hedge_replay_workspace_bytes(int B, int k, int nT, int nM, size_t* out);
+int psh_hedge_replay(int device, void* stream, const float* dlnx, int64_t row_stride, int B, int k, int len,
+                     const double* weights, double x_init, double rate, const int* Ts, int nT, const double* Ms, int nM,
+                     int degree, int kind, const double* policy, const double* strike, const double* centre,
+                     double* out_sums /* B x nT x nM x 9 */, double* out_pnl /* B x nT x nM x k, or NULL */,
+                     int32_t* out_status, void* workspace, size_t workspace_bytes);
+
+/*
  * Path generation of the discrete path-dependent volatility model (Guyon, Lekeufack 2024): S paths of n_steps steps for
  * each of B dates, one lane per path, in double.  The method, in full, heads shadowing_amd/csrc/psh_pdv.hip (and README
  * "PDV model"); shadowing_amd/pdv.py (PDVModelDiscrete.gen, pdv_future_paths) is its numpy twin.

@@ -14,7 +14,7 @@ from .plotting import plot_closest, plot_shadow, plot_volatility
 from .mrw import (MRWGenerator, SMRWGenerator, mrw_log_returns, smrw_kernel, smrw_leverage, smrw_log_returns,
                   smrw_sq_moment)
 from .pdv import AutoregressiveLinearPredictor, PDVModel, PDVModelDiscrete
-from .pricing import PriceData, Smile, compute_smile
+from .pricing import HedgedPnL, HedgePolicy, PriceData, Smile, compute_smile, hedge_pnl
 from .quantiles import PredictiveQuantiles, weighted_quantiles
 from .statistics import realized_variance
 from .stylized import LaggedMoments, fit_smrw, lagged_moments
@@ -25,7 +25,7 @@ __all__ = [
     "ArrayType", "ContextManagerBase", "PredictionContext", "ImputationContext", "CrossChannelContext",
     "PathEmbedding", "Identity", "Foveal", "PathDistance", "RelativeMSE", "PathShadowing",
     "select_cartesian_product", "DiscreteProba", "Softmax", "Uniform", "realized_variance",
-    "plot_closest", "plot_shadow", "plot_volatility", "PriceData", "Smile", "compute_smile",
+    "plot_closest", "plot_shadow", "plot_volatility", "PriceData", "Smile", "compute_smile", "hedge_pnl", "HedgePolicy", "HedgedPnL",
     "PDVModel", "PDVModelDiscrete", "AutoregressiveLinearPredictor",
     "MRWGenerator", "mrw_log_returns", "SMRWGenerator", "smrw_log_returns", "smrw_kernel", "smrw_leverage",
     "smrw_sq_moment", "LaggedMoments", "lagged_moments", "fit_smrw",

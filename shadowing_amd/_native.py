@@ -58,7 +58,8 @@ EXPORTS = ("psh_version", "psh_strerror", "psh_last_hip_error", "psh_workspace_b
            "psh_embedded_supported", "psh_embed_plan_offset", "psh_candidates_layout", "psh_workspace_init", "psh_last_comm_error", "psh_comm_unique_id", "psh_comm_create",
            "psh_comm_destroy", "psh_comm_world", "psh_exchange_merge", "psh_stream_create_reserving", "psh_stream_destroy",
            "psh_weighted_moments", "psh_realized_variance", "psh_count_nonfinite", "psh_smear_nonfinite", "psh_rows_nonfinite",
-           "psh_shadow_block_layout", "psh_shadow_blocking", "psh_hedged_mc", "psh_pdv_generate", "psh_mrw_generate", "psh_smrw_generate",
+           "psh_shadow_block_layout", "psh_shadow_blocking", "psh_hedged_mc", "psh_hmc_policy_doubles", "psh_hedged_mc_policy",
+           "psh_hedge_replay_workspace_bytes", "psh_hedge_replay", "psh_pdv_generate", "psh_mrw_generate", "psh_smrw_generate",
            "psh_lagged_moments", "psh_lagged_moments_workspace_bytes", "psh_scattering_spectra",
            "psh_scattering_spectra_workspace_bytes", "psh_scattering_vjp", "psh_scattering_vjp_workspace_bytes",
            "psh_weighted_quantiles", "psh_filter_copy_bytes", "psh_filter_copy_build", "psh_scan_topk_copy")
@@ -172,6 +173,15 @@ def load() -> C.CDLL:
     L.psh_hedged_mc.restype = i32
     L.psh_hedged_mc.argtypes = [i32, vp, vp, i64, i32, i32, i32, vp, C.c_double, C.c_double, C.POINTER(C.c_int), i32,
                                 C.POINTER(C.c_double), i32, i32, i32, vp, vp, vp, vp, vp]
+    L.psh_hedged_mc_policy.restype = i32
+    L.psh_hedged_mc_policy.argtypes = L.psh_hedged_mc.argtypes + [vp]
+    L.psh_hmc_policy_doubles.restype = i32
+    L.psh_hmc_policy_doubles.argtypes = [i32, i32, i32, i32, i32, C.POINTER(C.c_size_t)]
+    L.psh_hedge_replay_workspace_bytes.restype = i32
+    L.psh_hedge_replay_workspace_bytes.argtypes = [i32, i32, i32, i32, C.POINTER(C.c_size_t)]
+    L.psh_hedge_replay.restype = i32
+    L.psh_hedge_replay.argtypes = [i32, vp, vp, i64, i32, i32, i32, vp, C.c_double, C.c_double, C.POINTER(C.c_int), i32,
+                                   C.POINTER(C.c_double), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, C.c_size_t]
     L.psh_pdv_generate.restype = i32
     L.psh_pdv_generate.argtypes = [i32, vp, i32, i64, i32] + [C.POINTER(C.c_double)] * 6 + [i32, C.c_double, C.c_double,
                                                                                           C.c_double, vp, vp, vp, C.c_uint64,
@@ -1279,11 +1289,8 @@ def scattering_vjp(x: torch.Tensor, J: int, G: int, psi_hat: torch.Tensor, cot: 
     return grad, status
 
 
-def hedged_mc(dlnx: torch.Tensor, weights: torch.Tensor | None, Ts, Ms, x_init: float = 100.0, rate: float = 0.0,
-              degree: int = 3, kind: int = PSH_HMC_OTM) -> dict:
-    """psh_hedged_mc on a float32 HIP tensor of log-returns (B, k, L) whose rows lie a constant stride apart (contiguous,
-    or the out-context view `paths[:, :, c, W:]` of gathered paths -- no copy); weights (B, k) float64 or None (uniform).
-    Returns device tensors: price / iv / strike (B, nT, nM) float64, sigma (B, nT) float64, status (B,) int32."""
+def _hmc_inputs(dlnx, weights, Ts, Ms):
+    """The checks hedged_mc and hedge_replay share: (x, row_stride, weights tensor or None, Ts, Ms)."""
     x = dlnx
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
         raise NativeLibraryError(f"dlnx must be a tensor on a HIP device (got {type(x).__name__}); there is no CPU path here")
@@ -1296,26 +1303,76 @@ def hedged_mc(dlnx: torch.Tensor, weights: torch.Tensor | None, Ts, Ms, x_init: 
     if rows is None or rows[1] < L:
         x = x.contiguous()
         rows = _uniform_rows(x)
-    row_stride = rows[1]
-    w_ptr = None
+    w = None
     if weights is not None:
         w = _dev_tensor(weights, torch.float64, "weights")
         if tuple(w.shape) != (B, k):
             raise ValueError(f"weights must be (B, k) = ({B}, {k}), got {tuple(w.shape)}")
         if w.device != x.device:
             raise ValueError("weights and dlnx must be on the same device")
-        w_ptr = w.data_ptr()
-    Ts = [int(T) for T in Ts]
-    Ms = [float(M) for M in Ms]
+    return x, rows[1], w, [int(T) for T in Ts], [float(M) for M in Ms]
+
+
+def hedged_mc(dlnx: torch.Tensor, weights: torch.Tensor | None, Ts, Ms, x_init: float = 100.0, rate: float = 0.0,
+              degree: int = 3, kind: int = PSH_HMC_OTM, policy: bool = False) -> dict:
+    """psh_hedged_mc on a float32 HIP tensor of log-returns (B, k, L) whose rows lie a constant stride apart (contiguous,
+    or the out-context view `paths[:, :, c, W:]` of gathered paths -- no copy); weights (B, k) float64 or None (uniform).
+    Returns device tensors: price / iv / strike (B, nT, nM) float64, sigma (B, nT) float64, status (B,) int32.
+    policy=True: psh_hedged_mc_policy, which adds "policy" (B, nT, nM, max Ts, 2 degree + 4) float64 (include/psh.h)."""
+    x, row_stride, w, Ts, Ms = _hmc_inputs(dlnx, weights, Ts, Ms)
+    B, k, L = x.shape
+    w_ptr = None if w is None else w.data_ptr()
     nT, nM = len(Ts), len(Ms)
     out = {name: torch.empty((B, nT, nM), dtype=torch.float64, device=x.device) for name in ("price", "iv", "strike")}
     out["sigma"] = torch.empty((B, nT), dtype=torch.float64, device=x.device)
     out["status"] = torch.empty((B,), dtype=torch.int32, device=x.device)
-    _check(load().psh_hedged_mc(x.device.index, _stream_ptr(x.device), x.data_ptr(), row_stride, B, k, L, w_ptr,
-                                float(x_init), float(rate), (C.c_int * max(nT, 1))(*Ts), nT,
-                                (C.c_double * max(nM, 1))(*Ms), nM, int(degree), int(kind), out["price"].data_ptr(),
-                                out["iv"].data_ptr(), out["strike"].data_ptr(), out["sigma"].data_ptr(),
-                                out["status"].data_ptr()), "psh_hedged_mc")
+    args = (x.device.index, _stream_ptr(x.device), x.data_ptr(), row_stride, B, k, L, w_ptr,
+            float(x_init), float(rate), (C.c_int * max(nT, 1))(*Ts), nT,
+            (C.c_double * max(nM, 1))(*Ms), nM, int(degree), int(kind), out["price"].data_ptr(),
+            out["iv"].data_ptr(), out["strike"].data_ptr(), out["sigma"].data_ptr(),
+            out["status"].data_ptr())
+    if not policy:
+        _check(load().psh_hedged_mc(*args), "psh_hedged_mc")
+        return out
+    n = C.c_size_t(0)
+    _check(load().psh_hmc_policy_doubles(B, nT, nM, max(Ts, default=0), int(degree), C.byref(n)), "psh_hmc_policy_doubles")
+    out["policy"] = torch.empty((B, nT, nM, max(Ts), 2 * int(degree) + 4), dtype=torch.float64, device=x.device)
+    assert out["policy"].numel() == n.value
+    _check(load().psh_hedged_mc_policy(*args, out["policy"].data_ptr()), "psh_hedged_mc_policy")
+    return out
+
+
+def hedge_replay(dlnx: torch.Tensor, weights: torch.Tensor | None, Ts, Ms, policy: torch.Tensor, strike: torch.Tensor,
+                 centre: torch.Tensor, x_init: float = 100.0, rate: float = 0.0, degree: int = 3, kind: int = PSH_HMC_OTM,
+                 return_pnl: bool = False) -> dict:
+    """psh_hedge_replay: the policy (B, nT, nM, max Ts, 2 degree + 4) of a fit, with the fit's strike and price
+    (B, nT, nM) and its x_init, rate, Ts, Ms, degree, kind, replayed on float32 log-returns (B, k', L) (as hedged_mc's; any
+    k').  Returns device tensors: sums (B, nT, nM, 9) float64, status (B,) int32, and pnl (B, nT, nM, k') when asked for."""
+    x, row_stride, w, Ts, Ms = _hmc_inputs(dlnx, weights, Ts, Ms)
+    B, k, L = x.shape
+    nT, nM = len(Ts), len(Ms)
+    pol = _dev_tensor(policy, torch.float64, "policy").contiguous()
+    if tuple(pol.shape) != (B, nT, nM, max(Ts, default=0), 2 * int(degree) + 4):
+        raise ValueError(f"policy must be (B, nT, nM, max Ts, 2 degree + 4), got {tuple(pol.shape)}")
+    ks = _dev_tensor(strike, torch.float64, "strike").contiguous()
+    ce = _dev_tensor(centre, torch.float64, "centre").contiguous()
+    if tuple(ks.shape) != (B, nT, nM) or tuple(ce.shape) != (B, nT, nM):
+        raise ValueError(f"strike and centre must be (B, nT, nM) = ({B}, {nT}, {nM})")
+    if any(t.device != x.device for t in (pol, ks, ce)):
+        raise ValueError("policy, strike, centre and dlnx must be on the same device")
+    out = {"sums": torch.empty((B, nT, nM, 9), dtype=torch.float64, device=x.device),
+           "status": torch.empty((B,), dtype=torch.int32, device=x.device)}
+    if return_pnl:
+        out["pnl"] = torch.empty((B, nT, nM, k), dtype=torch.float64, device=x.device)
+    nbytes = C.c_size_t(0)
+    _check(load().psh_hedge_replay_workspace_bytes(B, k, nT, nM, C.byref(nbytes)), "psh_hedge_replay_workspace_bytes")
+    ws = torch.empty((max(nbytes.value, 8) + 7) // 8, dtype=torch.int64, device=x.device)
+    _check(load().psh_hedge_replay(x.device.index, _stream_ptr(x.device), x.data_ptr(), row_stride, B, k, L,
+                                   None if w is None else w.data_ptr(), float(x_init), float(rate),
+                                   (C.c_int * max(nT, 1))(*Ts), nT, (C.c_double * max(nM, 1))(*Ms), nM, int(degree),
+                                   int(kind), pol.data_ptr(), ks.data_ptr(), ce.data_ptr(), out["sums"].data_ptr(),
+                                   out["pnl"].data_ptr() if return_pnl else None, out["status"].data_ptr(),
+                                   ws.data_ptr(), ws.numel() * 8), "psh_hedge_replay")
     return out
 
 

@@ -1509,10 +1509,10 @@ int psh_weighted_quantiles(int device, void* stream, const float* values, const 
     return PSH_OK;
 }
 
-int psh_hedged_mc(int device, void* stream, const float* dlnx, int64_t row_stride, int B, int k, int len,
-                  const double* weights, double x_init, double rate, const int* Ts, int nT, const double* Ms, int nM,
-                  int degree, int kind, double* out_price, double* out_iv, double* out_strike, double* out_sigma,
-                  int32_t* out_status) {
+// the argument checks and the launch arguments that psh_hedged_mc and psh_hedged_mc_policy share
+static int hmc_fill_args(HmcArgs& a, const float* dlnx, int64_t row_stride, int B, int k, int len, const double* weights,
+                         double x_init, double rate, const int* Ts, int nT, const double* Ms, int nM, int degree, int kind,
+                         double* out_price, double* out_iv, double* out_strike, double* out_sigma, int32_t* out_status) {
     if (!dlnx || !Ts || !Ms || !out_price || !out_iv || !out_strike || B <= 0 || k <= 0 || len <= 0 || row_stride < len ||
         nT <= 0 || nM <= 0 || degree < 1 || kind < PSH_HMC_OTM || kind > PSH_HMC_PUT || !std::isfinite(x_init) ||
         !(x_init > 0.0) || !std::isfinite(rate))
@@ -1520,7 +1520,6 @@ int psh_hedged_mc(int device, void* stream, const float* dlnx, int64_t row_strid
     if (k > PSH_MAX_K || degree > 5 || nT > PSH_HMC_MAX_T || nM > PSH_HMC_MAX_M) return PSH_ERR_UNSUPPORTED;
     if ((int64_t)B * k * row_stride >= ((int64_t)1 << 40) || (int64_t)B * nT * ((nM + PSH_HMC_SG - 1) / PSH_HMC_SG) >= ((int64_t)1 << 31))
         return PSH_ERR_UNSUPPORTED;
-    HmcArgs a{};
     a.x = dlnx; a.row_stride = row_stride; a.B = B; a.k = k; a.len = len; a.w = weights; a.x_init = x_init; a.rate = rate;
     a.nT = nT; a.nM = nM; a.degree = degree; a.kind = kind; a.ngroups = (nM + PSH_HMC_SG - 1) / PSH_HMC_SG;
     for (int i = 0; i < nT; ++i) {
@@ -1532,8 +1531,84 @@ int psh_hedged_mc(int device, void* stream, const float* dlnx, int64_t row_strid
         a.Ms[i] = Ms[i];
     }
     a.price = out_price; a.iv = out_iv; a.strike = out_strike; a.sigma = out_sigma; a.status = out_status;
+    return PSH_OK;
+}
+
+int psh_hedged_mc(int device, void* stream, const float* dlnx, int64_t row_stride, int B, int k, int len,
+                  const double* weights, double x_init, double rate, const int* Ts, int nT, const double* Ms, int nM,
+                  int degree, int kind, double* out_price, double* out_iv, double* out_strike, double* out_sigma,
+                  int32_t* out_status) {
+    HmcArgs a{};
+    const int rc = hmc_fill_args(a, dlnx, row_stride, B, k, len, weights, x_init, rate, Ts, nT, Ms, nM, degree, kind,
+                                 out_price, out_iv, out_strike, out_sigma, out_status);
+    if (rc != PSH_OK) return rc;
     GUARD_DEVICE(device);
     HIP_TRY(launch_hedged_mc(a, (hipStream_t)stream));
+    return PSH_OK;
+}
+
+int psh_hmc_policy_doubles(int B, int nT, int nM, int Tmax, int degree, size_t* out) {
+    if (!out || B <= 0 || nT <= 0 || nM <= 0 || Tmax <= 0 || degree < 1) return PSH_ERR_ARG;
+    if (degree > 5 || nT > PSH_HMC_MAX_T || nM > PSH_HMC_MAX_M) return PSH_ERR_UNSUPPORTED;
+    *out = (size_t)B * nT * nM * Tmax * (2 * degree + 4);
+    return PSH_OK;
+}
+
+int psh_hedged_mc_policy(int device, void* stream, const float* dlnx, int64_t row_stride, int B, int k, int len,
+                         const double* weights, double x_init, double rate, const int* Ts, int nT, const double* Ms, int nM,
+                         int degree, int kind, double* out_price, double* out_iv, double* out_strike, double* out_sigma,
+                         int32_t* out_status, double* out_policy) {
+    if (!out_policy) return PSH_ERR_ARG;
+    HmcArgs a{};
+    const int rc = hmc_fill_args(a, dlnx, row_stride, B, k, len, weights, x_init, rate, Ts, nT, Ms, nM, degree, kind,
+                                 out_price, out_iv, out_strike, out_sigma, out_status);
+    if (rc != PSH_OK) return rc;
+    GUARD_DEVICE(device);
+    HIP_TRY(launch_hedged_mc_policy(a, out_policy, (hipStream_t)stream));
+    return PSH_OK;
+}
+
+int psh_hedge_replay_workspace_bytes(int B, int k, int nT, int nM, size_t* out) {
+    if (!out || B <= 0 || k <= 0 || nT <= 0 || nM <= 0) return PSH_ERR_ARG;
+    if (nT > PSH_HMC_MAX_T || nM > PSH_HMC_MAX_M) return PSH_ERR_UNSUPPORTED;
+    const size_t ntiles = ((size_t)k + PSH_HEDGE_TILE - 1) / PSH_HEDGE_TILE;
+    *out = (size_t)B * nT * nM * ntiles * PSH_HEDGE_NPART * sizeof(double);
+    return PSH_OK;
+}
+
+int psh_hedge_replay(int device, void* stream, const float* dlnx, int64_t row_stride, int B, int k, int len,
+                     const double* weights, double x_init, double rate, const int* Ts, int nT, const double* Ms, int nM,
+                     int degree, int kind, const double* policy, const double* strike, const double* centre,
+                     double* out_sums, double* out_pnl, int32_t* out_status, void* workspace, size_t workspace_bytes) {
+    if (!dlnx || !Ts || !Ms || !policy || !strike || !centre || !out_sums || !workspace || B <= 0 || k <= 0 || len <= 0 ||
+        row_stride < len || nT <= 0 || nM <= 0 || degree < 1 || kind < PSH_HMC_OTM || kind > PSH_HMC_PUT ||
+        !std::isfinite(x_init) || !(x_init > 0.0) || !std::isfinite(rate))
+        return PSH_ERR_ARG;
+    if (degree > 5 || nT > PSH_HMC_MAX_T || nM > PSH_HMC_MAX_M) return PSH_ERR_UNSUPPORTED;
+    HedgeReplayArgs a{};
+    a.ngroups = (nM + PSH_HMC_SG - 1) / PSH_HMC_SG;
+    a.ntiles = (int)(((int64_t)k + PSH_HEDGE_TILE - 1) / PSH_HEDGE_TILE);
+    if ((int64_t)B * k * row_stride >= ((int64_t)1 << 40) || (int64_t)B * nT * a.ngroups * a.ntiles >= ((int64_t)1 << 31))
+        return PSH_ERR_UNSUPPORTED;
+    for (int i = 0; i < nT; ++i) {
+        if (Ts[i] < 1 || Ts[i] > len) return PSH_ERR_ARG;
+        a.Ts[i] = Ts[i];
+        a.Tmax = Ts[i] > a.Tmax ? Ts[i] : a.Tmax;
+    }
+    for (int i = 0; i < nM; ++i) {
+        if (!std::isfinite(Ms[i])) return PSH_ERR_ARG;
+        a.Ms[i] = Ms[i];
+    }
+    if (hedge_replay_lds_bytes(a.Tmax, degree) > PSH_HEDGE_MAX_LDS) return PSH_ERR_UNSUPPORTED;   // (the policy rows sit in LDS)
+    size_t need = 0;
+    psh_hedge_replay_workspace_bytes(B, k, nT, nM, &need);
+    if (workspace_bytes < need) return PSH_ERR_WORKSPACE;
+    a.x = dlnx; a.row_stride = row_stride; a.B = B; a.k = k; a.len = len; a.w = weights; a.x_init = x_init; a.rate = rate;
+    a.nT = nT; a.nM = nM; a.degree = degree; a.kind = kind;
+    a.policy = policy; a.strike = strike; a.centre = centre; a.sums = out_sums; a.pnl = out_pnl; a.status = out_status;
+    a.part = (double*)workspace;
+    GUARD_DEVICE(device);
+    HIP_TRY(launch_hedge_replay(a, (hipStream_t)stream));
     return PSH_OK;
 }
 

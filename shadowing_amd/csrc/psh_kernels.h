@@ -437,6 +437,32 @@ struct HmcArgs {
 };
 hipError_t launch_hedged_mc(const HmcArgs& a, hipStream_t s);
 
+// psh_hmc_report.hip: the fit with its policy kept (psh_hedged_mc_policy) and the replay of a policy (psh_hedge_replay)
+#define PSH_HEDGE_TILE 512        // paths of a replay workgroup: a constant, so the sums do not depend on the grid
+#define PSH_HEDGE_NSUM 9          // a1 a2 b1 b2 p1 p2 q1 q2 s2 (include/psh.h)
+#define PSH_HEDGE_NPART 11        // a tile's partials: sum w, the nine sums with raw weights, the tile's status bits
+#define PSH_HEDGE_MAX_LDS (160 * 1024)
+hipError_t launch_hedged_mc_policy(const HmcArgs& a, double* policy, hipStream_t s);
+struct HedgeReplayArgs {
+    const float* x;           // row b * k + i starts at x + (b * k + i) * row_stride
+    int64_t row_stride;
+    int B, k, len;
+    const double* w;          // (B, k), or nullptr: uniform
+    double x_init, rate;
+    int nT, nM, degree, kind, ngroups, Tmax, ntiles;
+    int Ts[PSH_HMC_MAX_T];
+    double Ms[PSH_HMC_MAX_M];
+    const double* policy;     // (B, nT, nM, Tmax, 2 degree + 4)
+    const double* strike;     // (B, nT, nM): the fit's
+    const double* centre;     // (B, nT, nM): the fit's price
+    double* sums;             // (B, nT, nM, PSH_HEDGE_NSUM)
+    double* pnl;              // (B, nT, nM, k) or nullptr
+    int32_t* status;          // (B) or nullptr
+    double* part;             // workspace: (B, nT, nM, ntiles, PSH_HEDGE_NPART)
+};
+size_t hedge_replay_lds_bytes(int T, int degree);
+hipError_t launch_hedge_replay(const HedgeReplayArgs& a, hipStream_t s);
+
 // psh_pdv.hip: path generation of the discrete PDV model (psh_pdv_generate)
 struct PdvArgs {
     int64_t n_paths, S;       // B * S paths, S per date

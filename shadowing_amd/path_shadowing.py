@@ -990,10 +990,12 @@ class PathShadowing:
         return np.ascontiguousarray(np.broadcast_to(w, distances.shape), dtype=np.float64)
 
     def smile_from_paths(self, distances: np.ndarray, paths, Ts, Ms, proba_name: str = "softmax", eta: float | None = None,
-                         r: float = 0.0, x_init: float = 100.0, channel: int = 0, degree: int = 3, kind: str = "otm"):
+                         r: float = 0.0, x_init: float = 100.0, channel: int = 0, degree: int = 3, kind: str = "otm",
+                         report: bool = False):
         """Hedged Monte Carlo smile (pricing.compute_smile) of the out-context of the k shadowing paths of every query,
         weighted by the averaging class, as predict_from_paths() weighs its statistic.  `paths` (B, k, C, T_x + h) are
-        log-returns; prices start at x_init.  Numpy paths take the host path, HIP tensors the psh_hedged_mc kernel."""
+        log-returns; prices start at x_init.  Numpy paths take the host path, HIP tensors the psh_hedged_mc kernel.
+        report=True: the Smile's report fields (delta, risk, standard errors, policy) are filled."""
         if not isinstance(self.context, PredictionContext):
             raise NotImplementedError("smile_from_paths: only a PredictionContext has an out-context to price on")
         from .pricing import smile_from_log_returns
@@ -1001,16 +1003,18 @@ class PathShadowing:
         d = distances.detach().cpu().numpy() if isinstance(distances, torch.Tensor) else np.asarray(distances)
         w = self._smile_weights(proba_name, d, eta)
         cuda = isinstance(future, torch.Tensor) and future.is_cuda
-        return smile_from_log_returns(future, w, Ts, Ms, x_init, r, degree=degree, kind=kind, cuda=cuda)
+        return smile_from_log_returns(future, w, Ts, Ms, x_init, r, degree=degree, kind=kind, cuda=cuda, report=report)
 
     def smile(self, x_context: ArrayType, k: int, Ts, Ms, eta: float | None = None, proba_name: str = "softmax",
               r: float = 0.0, x_init: float = 100.0, channel: int = 0, degree: int = 3, kind: str = "otm",
-              n_dataset_splits: int = 1, n_context_splits: int = 1, cuda: bool = False):
+              n_dataset_splits: int = 1, n_context_splits: int = 1, cuda: bool = False, report: bool = False):
         """shadow() + smile_from_paths() over `n_context_splits` batches of queries.  With cuda=True on a natively scanned
         configuration the gathered paths stay in HBM: the (B, k) distances come to the host for the averaging class's
         weights, the weights go back up, psh_hedged_mc prices on the out-context view of the paths, and only the
-        (B, nT, nM) results come down.  Anything else (k > PSH_MAX_K included) prices the host results of shadow()."""
-        from .pricing import Smile, smile_from_log_returns
+        (B, nT, nM) results come down.  Anything else (k > PSH_MAX_K included) prices the host results of shadow().
+        report=True: the fit keeps its policy and psh_hedge_replay replays it on the same view -- the paths and the policy
+        (Smile.policy.coef, a HIP tensor) stay in HBM, the (B, nT, nM) report fields come down."""
+        from .pricing import concat_smiles, smile_from_log_returns
         if not isinstance(self.context, PredictionContext):
             raise NotImplementedError("smile: only a PredictionContext has an out-context to price on")
         x = _torch(_dim_array(x_context))
@@ -1030,14 +1034,12 @@ class PathShadowing:
                     w = self._smile_weights(proba_name, d_host, eta)
                     wt = None if w is None else torch.from_numpy(w.copy()).to(paths.device)
                     future = self.context.select_out_context(paths)[:, :, channel, :]
-                    parts.append(smile_from_log_returns(future, wt, Ts, Ms, x_init, r, degree=degree, kind=kind, cuda=True))
+                    parts.append(smile_from_log_returns(future, wt, Ts, Ms, x_init, r, degree=degree, kind=kind, cuda=True,
+                                                        report=report))
                     continue
             d, paths, _ = self.shadow(xr, k, n_dataset_splits, cuda)
-            parts.append(self.smile_from_paths(d, paths, Ts, Ms, proba_name, eta, r, x_init, channel, degree, kind))
-        cat = lambda name: np.concatenate([getattr(p, name) for p in parts])   # noqa: E731
-        p0 = parts[0]
-        return Smile(cat("prices"), cat("ivs"), cat("strikes"), cat("sigma"), p0.Ts, p0.Ms, kind, cat("status"),
-                     p0.x_init, p0.r)
+            parts.append(self.smile_from_paths(d, paths, Ts, Ms, proba_name, eta, r, x_init, channel, degree, kind, report))
+        return concat_smiles(parts)
 
 
 _MOMENT_CLASSES: dict = {}      # averaging class -> its avg / std ARE the weighted moments of its `weights` (probed once)
