@@ -382,6 +382,64 @@ def _filter_copy_auto(ds: torch.Tensor):
     return ent["copy"]
 
 
+def _per_launch(B: int, out, call):
+    """(d, idx, status) of `call(queries' slice, that slice of out)` over PSH_MAX_B_PER_LAUNCH queries at a time, concatenated: one
+    launch keeps a per-block append cursor per query in LDS."""
+    cuts = [slice(i, i + PSH_MAX_B_PER_LAUNCH) for i in range(0, B, PSH_MAX_B_PER_LAUNCH)]
+    parts = [call(c, None if out is None else tuple(o[c] for o in out)) for c in cuts]
+    return tuple(torch.cat([p[j] for p in parts], dim=0) for j in range(3))
+
+
+def _cut(t, c):
+    return None if t is None else t[c].contiguous()
+
+
+def _scan_outputs(out, B: int, k: int, dev):
+    """(d (B,k) f32, idx (B,k,2) i32, status (B,) i32) of a scan: the caller's contiguous device tensors (e.g. views of a send
+    buffer; the status words optionally, as out[2] -- no allocation at all in the call then) or fresh ones."""
+    status = None
+    if out is not None:
+        out_d = _dev_tensor(out[0], torch.float32, "out[0]")
+        out_idx = _dev_tensor(out[1], torch.int32, "out[1]")
+        if tuple(out_d.shape) != (B, k) or tuple(out_idx.shape) != (B, k, 2):
+            raise ValueError("out must be ((B,k) float32, (B,k,2) int32)")
+        if len(out) > 2:
+            status = _dev_tensor(out[2], torch.int32, "out[2]")
+            if tuple(status.shape) != (B,):
+                raise ValueError("out[2] must be (B,) int32")
+    else:
+        out_d = torch.empty((B, k), dtype=torch.float32, device=dev)
+        out_idx = torch.empty((B, k, 2), dtype=torch.int32, device=dev)
+    if status is None:
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+    return out_d, out_idx, status
+
+
+def _scan_profile(B: int, profile: bool, scan_events, flags: int, info, tau_hint):
+    """The PshProfile a scan hands to the library (None: nothing to say): stage timings (`profile`), the two events around the
+    scan kernel, PSH_FLAG_* bits, the launch plan's facts for `info`, the caller's admission levels."""
+    prof = None
+    if profile:
+        prof = PshProfile()
+        prof.mode = 0
+    elif scan_events is not None:
+        prof = PshProfile()
+        prof.mode = 1
+        prof.ev_scan_begin = scan_events[0].cuda_event
+        prof.ev_scan_end = scan_events[1].cuda_event
+    if tau_hint is not None:
+        tau_hint = _dev_tensor(tau_hint, torch.float32, "tau_hint")
+        if tuple(tau_hint.shape) != (B,):
+            raise ValueError("tau_hint must be (B,) float32")
+    if flags or info is not None or tau_hint is not None:
+        if prof is None:
+            prof = PshProfile()
+            prof.mode = 1                 # no events given: nothing is recorded, nothing is synchronised
+        prof.flags = flags
+        prof.tau_hint = None if tau_hint is None else tau_hint.data_ptr()
+    return prof
+
+
 def scan_topk(dataset: torch.Tensor, queries: torch.Tensor, k: int, h: int = 0, r_offset: int = 0,
               qnorm: torch.Tensor | None = None, workspace: Workspace | None = None,
               exhaustive: bool = False, profile: bool = False, extra_workspace_factor: float = 1.0,
@@ -419,52 +477,15 @@ def scan_topk(dataset: torch.Tensor, queries: torch.Tensor, k: int, h: int = 0, 
     if qnorm is not None:
         qnorm = _dev_tensor(qnorm, torch.float32, "qnorm")
     if B > PSH_MAX_B_PER_LAUNCH and not profile and scan_events is None:
-        # one launch keeps a per-block append cursor per query in LDS: batch the queries
-        parts = [scan_topk(ds, q[i:i + PSH_MAX_B_PER_LAUNCH].contiguous(), k, h=h, r_offset=r_offset,
-                           qnorm=None if qnorm is None else qnorm[i:i + PSH_MAX_B_PER_LAUNCH].contiguous(),
-                           workspace=workspace, exhaustive=exhaustive, extra_workspace_factor=extra_workspace_factor,
-                           unsorted=unsorted, flags=flags,
-                           tau_hint=None if tau_hint is None else tau_hint[i:i + PSH_MAX_B_PER_LAUNCH].contiguous())
-                 for i in range(0, B, PSH_MAX_B_PER_LAUNCH)]
-        return tuple(torch.cat([p[j] for p in parts], dim=0) for j in range(3))
+        return _per_launch(B, out, lambda c, o: scan_topk(
+            ds, q[c].contiguous(), k, h=h, r_offset=r_offset, qnorm=_cut(qnorm, c), workspace=workspace, exhaustive=exhaustive,
+            extra_workspace_factor=extra_workspace_factor, out=o, unsorted=unsorted, flags=flags, tau_hint=_cut(tau_hint, c)))
     nbytes = int(workspace_bytes(R, T, B, W, h, k) * extra_workspace_factor)
     ws = (workspace or Workspace(dev)).get(nbytes)
-    status = None
-    if out is not None:       # caller-provided (B,k) f32 / (B,k,2) i32 contiguous device tensors (e.g. views of a send buffer)
-        out_d = _dev_tensor(out[0], torch.float32, "out[0]")
-        out_idx = _dev_tensor(out[1], torch.int32, "out[1]")
-        if tuple(out_d.shape) != (B, k) or tuple(out_idx.shape) != (B, k, 2):
-            raise ValueError("out must be ((B,k) float32, (B,k,2) int32)")
-        if len(out) > 2:      # ... and optionally the (B,) int32 status words (no allocation at all in the call then)
-            status = _dev_tensor(out[2], torch.int32, "out[2]")
-            if tuple(status.shape) != (B,):
-                raise ValueError("out[2] must be (B,) int32")
-    else:
-        out_d = torch.empty((B, k), dtype=torch.float32, device=dev)
-        out_idx = torch.empty((B, k, 2), dtype=torch.int32, device=dev)
-    if status is None:
-        status = torch.empty((B,), dtype=torch.int32, device=dev)
-    prof = None
-    if profile:
-        prof = PshProfile()
-        prof.mode = 0
-    elif scan_events is not None:
-        prof = PshProfile()
-        prof.mode = 1
-        prof.ev_scan_begin = scan_events[0].cuda_event
-        prof.ev_scan_end = scan_events[1].cuda_event
+    out_d, out_idx, status = _scan_outputs(out, B, k, dev)
     if unsorted and not exhaustive:
         flags |= FLAG_UNSORTED
-    if tau_hint is not None:
-        tau_hint = _dev_tensor(tau_hint, torch.float32, "tau_hint")
-        if tuple(tau_hint.shape) != (B,):
-            raise ValueError("tau_hint must be (B,) float32")
-    if flags or info is not None or tau_hint is not None:
-        if prof is None:
-            prof = PshProfile()
-            prof.mode = 1                 # no events given: nothing is recorded, nothing is synchronised
-        prof.flags = flags
-        prof.tau_hint = None if tau_hint is None else tau_hint.data_ptr()
+    prof = _scan_profile(B, profile, scan_events, flags, info, tau_hint)
     # the resident f16 copy serves one route only: everything else does not even look for one
     fc = None
     if filter_copy is not None and B == 1 and W <= 33 and (flags & FLAG_OVERLAP) and not (flags & (FLAG_FILTER_VALU | FLAG_NO_FUSE)) \
@@ -525,6 +546,24 @@ def scan_topk_checked(dataset: torch.Tensor, queries: torch.Tensor, k: int, h: i
     return d, idx
 
 
+def scan_topk_embedded_checked(dataset: torch.Tensor, kernel: torch.Tensor, hx: torch.Tensor, k: int, h: int = 0, r_offset: int = 0,
+                               workspace: Workspace | None = None, out: tuple | None = None, flags: int = 0,
+                               keep_plan: bool = False):
+    """scan_topk_embedded + its status protocol, ONE host synchronisation: the queries whose status is not OK (candidate slices
+    overflowed: massive ties / adversarial data) are redone through the exhaustive scan with the same `flags`.
+    Returns (d, idx) device tensors holding valid results for every query."""
+    ws = workspace or Workspace(dataset.device)
+    d, idx, status = scan_topk_embedded(dataset, kernel, hx, k, h=h, r_offset=r_offset, workspace=ws, out=out, flags=flags,
+                                        keep_plan=keep_plan)
+    bad = torch.nonzero(status != PSH_STATUS_OK).flatten()
+    if bad.numel():
+        d2, i2, _ = scan_topk_embedded(dataset, kernel, hx[bad].contiguous(), k, h=h, r_offset=r_offset, workspace=ws,
+                                       exhaustive=True, flags=flags)
+        d[bad] = d2
+        idx[bad] = i2
+    return d, idx
+
+
 PSH_EMB_MAX_D = 128
 
 
@@ -565,12 +604,9 @@ def scan_topk_embedded(dataset: torch.Tensor, kernel: torch.Tensor, hx: torch.Te
     if hxnorm is not None:
         hxnorm = _dev_tensor(hxnorm, torch.float32, "hxnorm")
     if B > PSH_MAX_B_PER_LAUNCH and not profile:
-        parts = [scan_topk_embedded(ds, ker, q[i:i + PSH_MAX_B_PER_LAUNCH].contiguous(), k, h=h, r_offset=r_offset,
-                                    hxnorm=None if hxnorm is None else hxnorm[i:i + PSH_MAX_B_PER_LAUNCH].contiguous(),
-                                    workspace=workspace, exhaustive=exhaustive, flags=flags, keep_plan=keep_plan,
-                                    tau_hint=None if tau_hint is None else tau_hint[i:i + PSH_MAX_B_PER_LAUNCH].contiguous())
-                 for i in range(0, B, PSH_MAX_B_PER_LAUNCH)]
-        return tuple(torch.cat([p[j] for p in parts], dim=0) for j in range(3))
+        return _per_launch(B, out, lambda c, o: scan_topk_embedded(
+            ds, ker, q[c].contiguous(), k, h=h, r_offset=r_offset, hxnorm=_cut(hxnorm, c), workspace=workspace,
+            exhaustive=exhaustive, out=o, flags=flags, keep_plan=keep_plan, tau_hint=_cut(tau_hint, c)))
     wsobj = workspace or Workspace(dev)
     ws = wsobj.get(workspace_bytes(R, T, B, K, h, k))
     if not exhaustive:
@@ -580,29 +616,8 @@ def scan_topk_embedded(dataset: torch.Tensor, kernel: torch.Tensor, hx: torch.Te
             flags |= FLAG_EMBED_PLAN_KEEP
         # (a call of the non-exhaustive entry point leaves the plan of ITS kernel in the workspace, unless it kept one)
         wsobj.plan_of = (kernel, kernel._version, B) if planned else None
-    if out is not None:
-        out_d = _dev_tensor(out[0], torch.float32, "out[0]")
-        out_idx = _dev_tensor(out[1], torch.int32, "out[1]")
-        if tuple(out_d.shape) != (B, k) or tuple(out_idx.shape) != (B, k, 2):
-            raise ValueError("out must be ((B,k) float32, (B,k,2) int32)")
-    else:
-        out_d = torch.empty((B, k), dtype=torch.float32, device=dev)
-        out_idx = torch.empty((B, k, 2), dtype=torch.int32, device=dev)
-    status = torch.empty((B,), dtype=torch.int32, device=dev)
-    prof = None
-    if profile:
-        prof = PshProfile()
-        prof.mode = 0
-    if tau_hint is not None:
-        tau_hint = _dev_tensor(tau_hint, torch.float32, "tau_hint")
-        if tuple(tau_hint.shape) != (B,):
-            raise ValueError("tau_hint must be (B,) float32")
-    if flags or tau_hint is not None or info is not None:
-        if prof is None:
-            prof = PshProfile()
-            prof.mode = 1
-        prof.flags = flags
-        prof.tau_hint = None if tau_hint is None else tau_hint.data_ptr()
+    out_d, out_idx, status = _scan_outputs(out, B, k, dev)
+    prof = _scan_profile(B, profile, None, flags, info, tau_hint)
     name = "psh_scan_topk_embedded_exhaustive" if exhaustive else "psh_scan_topk_embedded"
     rc = getattr(load(), name)(dev.index, _stream_ptr(dev), ds.data_ptr(), R, T, r_offset, ker.data_ptr(), d, K,
                                q.data_ptr(), None if hxnorm is None else hxnorm.data_ptr(), B, h, k,

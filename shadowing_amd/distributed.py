@@ -21,6 +21,7 @@ import torch
 import torch.distributed as dist
 
 from . import _native
+from ._dirty import DirtyRows
 from .path_distance import RelativeMSE
 from .path_embedding import Identity, PathEmbedding, PredictionContext
 
@@ -46,23 +47,21 @@ def _native_local_topk(ds2d: torch.Tensor, q: torch.Tensor, k: int, h: int, r_of
                        out=None, check: bool = True, ker: torch.Tensor | None = None, unsorted: bool = False, flags: int = 0):
     """q: the query windows (B, W), or -- with `ker` (d, K), a linear embedding -- the embedded
     queries (B, d)."""
-    def run(qq, exhaustive, out_):
-        if ker is None:
-            return _native.scan_topk(ds2d, qq, k, h=h, r_offset=r_offset, workspace=workspace, out=out_,
-                                     exhaustive=exhaustive, unsorted=unsorted, flags=flags)
-        return _native.scan_topk_embedded(ds2d, ker, qq, k, h=h, r_offset=r_offset, workspace=workspace, out=out_,
-                                          exhaustive=exhaustive, flags=flags & _native.FLAG_EMBED_MX)
-    if check and ker is None:    # one host sync: the status protocol (fused launch gave up -> separate launches; overflow -> exact)
-        d, idx = _native.scan_topk_checked(ds2d, q, k, h=h, r_offset=r_offset, workspace=workspace, out=out, unsorted=unsorted,
-                                           flags=flags)
-        return d, idx, torch.zeros((q.shape[0],), dtype=torch.int32, device=q.device)
-    d, idx, status = run(q, False, out)
-    if check:    # one host sync: a query whose candidate slices overflowed is redone exactly
-        bad = torch.nonzero(status != _native.PSH_STATUS_OK).flatten()
-        if bad.numel():
-            d2, idx2, _ = run(q[bad].contiguous(), True, None)
-            d[bad] = d2
-            idx[bad] = idx2
+    if ker is None:
+        if check:    # one host sync: the status protocol (fused launch gave up -> separate launches; overflow -> exact)
+            d, idx = _native.scan_topk_checked(ds2d, q, k, h=h, r_offset=r_offset, workspace=workspace, out=out, unsorted=unsorted,
+                                               flags=flags)
+            return d, idx, torch.zeros((q.shape[0],), dtype=torch.int32, device=q.device)
+        return _native.scan_topk(ds2d, q, k, h=h, r_offset=r_offset, workspace=workspace, out=out, unsorted=unsorted, flags=flags)
+    flags &= _native.FLAG_EMBED_MX
+    if not check:
+        return _native.scan_topk_embedded(ds2d, ker, q, k, h=h, r_offset=r_offset, workspace=workspace, out=out, flags=flags)
+    # one host sync: a query whose candidate slices overflowed is redone exactly; the sampled call's status words come back
+    B = q.shape[0]
+    status = torch.empty((B,), dtype=torch.int32, device=q.device)
+    out = out or (torch.empty((B, k), dtype=torch.float32, device=q.device), torch.empty((B, k, 2), dtype=torch.int32, device=q.device))
+    d, idx = _native.scan_topk_embedded_checked(ds2d, ker, q, k, h=h, r_offset=r_offset, workspace=workspace,
+                                                out=(out[0], out[1], status), flags=flags)
     return d, idx, status
 
 
@@ -165,18 +164,10 @@ class ShardedPathShadowing:
         dirty = bool(local_topk is None and self.dataset.numel() and _native.count_nonfinite(self.dataset))
         self._dirty_split = None
         if dirty and self._linear:
-            # NaN / +-inf samples behind a linear embedding (round 6: served, no longer refused): the embedded scans' rejection
-            # tests assume finite data (prefix sums and matrix-core tiles spread a NaN over clean windows), so THIS rank scans its
-            # clean rows as ever and its dirty rows -- the horizon smeared in -- with the exhaustive dense chains, which meet a NaN
-            # exactly where the reference's zero-padded conv does (ref path_embedding.py:48-51, :129-132), and merges the two
-            # lists before the exchange: PathShadowing._split_dirty_rows per shard.  No rank has to know about another's shard.
-            back = int(self.context.get_out_times())
-            flags_ = _native.rows_nonfinite(self.dataset)
-            dirty_idx = torch.nonzero(flags_).flatten()
-            clean_idx = torch.nonzero(flags_ == 0).flatten()
-            clean_rows = self.dataset[clean_idx, 0, :].contiguous()
-            dirty_rows = _native.smear_nonfinite(self.dataset[dirty_idx].contiguous(), back, 0)
-            self._dirty_split = (clean_idx, clean_rows, dirty_idx, dirty_rows)
+            # NaN / +-inf samples behind a linear embedding: THIS rank scans its clean rows as ever and its dirty rows -- the horizon
+            # smeared in -- with the exhaustive dense chains, and merges the two lists before the exchange (_dirty.DirtyRows, as
+            # PathShadowing does, per shard).  No rank has to know about another's shard.
+            self._dirty_split = DirtyRows(self.dataset, int(self.context.get_out_times()))
             dirty = False                               # (self._rows is not used by the split scan)
         if dirty:
             self._rows = _native.smear_nonfinite(self.dataset, int(self.context.get_out_times()), 0)
@@ -323,7 +314,9 @@ class ShardedPathShadowing:
             d, idx = self._local_topk(self.dataset[:, 0, :], q, k_local, h, self.row_offset)
             status = None
         elif self._dirty_split is not None:
-            d, idx = self._split_local_topk(q, k_local, h, workspace or self._workspace, flags)
+            # (one host synchronisation: the rare path)
+            d, idx = self._dirty_split.topk(q, self._ker, k_local, h, workspace or self._workspace, flags & _native.FLAG_EMBED_MX,
+                                            row_offset=self.row_offset)
             status = torch.zeros((q.shape[0],), dtype=torch.int32, device=self.device)
             if out is not None and k_local == k:
                 out[0].copy_(d)
@@ -338,33 +331,6 @@ class ShardedPathShadowing:
             d = torch.cat([d, d.new_full((B, k - k_local), float("inf"))], dim=1)
             idx = torch.cat([idx, idx.new_full((B, k - k_local, 2), -1)], dim=1)
         return d.contiguous(), idx.contiguous(), status
-
-    def _split_local_topk(self, hx: torch.Tensor, k_local: int, h: int, workspace, flags: int):
-        """This rank's k_local best behind a linear embedding when its shard holds non-finite samples: the clean rows through the
-        embedded scan (status protocol: a query whose slices overflow is redone exactly), the dirty rows -- smeared -- through the
-        exhaustive dense chains, the two lists merged by (d, r, t); row numbers global.  One host synchronisation (rare path)."""
-        clean_idx, clean_rows, dirty_idx, dirty_rows = self._dirty_split
-        Tp = self.dataset.shape[-1] - self._ker.shape[-1] - h + 1
-        n_clean, n_dirty = int(clean_idx.numel()) * Tp, int(dirty_idx.numel()) * Tp
-        parts_d, parts_i = [], []
-        if n_clean > 0:
-            kc = min(k_local, n_clean)
-            dc, ic, _ = _native_local_topk(clean_rows, hx, kc, h, 0, workspace, check=True, ker=self._ker, flags=flags)
-            ic = ic.clone()
-            ic[..., 0] = (clean_idx[ic[..., 0].long()] + self.row_offset).to(torch.int32)
-            parts_d.append(dc)
-            parts_i.append(ic)
-        if n_dirty > 0:
-            kd = min(k_local, n_dirty)
-            dd, idd, _ = _native.scan_topk_embedded(dirty_rows, self._ker, hx, kd, h=h, workspace=workspace, exhaustive=True,
-                                                    flags=_native.FLAG_EMBED_DENSE)
-            idd = idd.clone()
-            idd[..., 0] = (dirty_idx[idd[..., 0].long()] + self.row_offset).to(torch.int32)
-            parts_d.append(dd)
-            parts_i.append(idd)
-        if len(parts_d) == 1 and parts_d[0].shape[1] == k_local:
-            return parts_d[0].contiguous(), parts_i[0].contiguous()
-        return _native.merge_topk(torch.cat(parts_d, dim=1).contiguous(), torch.cat(parts_i, dim=1).contiguous(), k_local)
 
     def scan(self, queries: torch.Tensor, k: int, check: bool = True):
         """Collective.  queries (B, W) float32 (same on every rank).  Returns device

@@ -35,6 +35,7 @@ import torch
 from tqdm import tqdm
 
 from . import _native
+from ._dirty import DirtyRows
 from .averaging import HAVE_SCATSPECTRA, DiscreteProba, Softmax, Uniform
 from .path_distance import PathDistance, RelativeMSE
 from .path_embedding import (ArrayType, ContextManagerBase, CrossChannelContext, Foveal, Identity, ImputationContext,
@@ -135,7 +136,7 @@ class PathShadowing:
         self._resident = None       # (key, device tensor (R, C, T), weakref to the host tensor) -- the ensemble in HBM
         self._scan_rows = None      # (key, device tensor (R, T)): channel 0 of a multi-channel ensemble
         self._dirty = False         # the resident ensemble holds NaN / +-inf samples (set by _scan_rows_of)
-        self._dirty_split = None    # (back, clean rows' indices, their rows, dirty rows' indices, their smeared rows): _split_dirty_rows
+        self._dirty_split = None    # _dirty.DirtyRows: the resident ensemble's clean and dirty rows behind a linear embedding
         self._served_by = "hip"     # what the last _native_scan ran: "hip", or "torch" (a dirty ensemble behind a linear embedding)
         self._gen = 0               # bumped by refresh()
         self._workspace = None
@@ -328,7 +329,7 @@ class PathShadowing:
         # ds[:, None, :] view of a 2-D CUDA dataset on every call, and a key that wanted the same object recounted the whole
         # ensemble -- a pass over it plus a host synchronisation -- on every shadow() call.  The cache keeps `ds` alive, so the
         # address cannot be handed to another tensor while the entry exists.
-        # (`smear` False: a linear embedding's scan never reads the smeared copy -- its dirty rows go through _split_dirty_rows --
+        # (`smear` False: a linear embedding's scan never reads the smeared copy -- its dirty rows go through _dirty.DirtyRows --
         #  so a dirty ensemble does not pay for a second R x T array it would not use)
         key = (ds.data_ptr(), tuple(ds.shape), tuple(ds.stride()), ds._version, back, str(ds.device), bool(smear))
         if self._scan_rows is None or self._scan_rows[0] != key:
@@ -342,21 +343,6 @@ class PathShadowing:
             self._scan_rows = (key, rows, ds)
         return self._scan_rows[1]
 
-    def _split_dirty_rows(self, ds: torch.Tensor, back: int):
-        """A dirty ensemble behind a linear embedding, once per resident copy: (clean row indices, their rows (Rc, T) as a
-        contiguous copy, dirty row indices, THEIR rows with every non-finite sample written back over the `back` samples before
-        it).  The embedded scans' rejection tests assume finite data (prefix sums and matrix-core tiles spread a NaN over clean
-        windows); the dense chains of the exhaustive path multiply all K taps, zeros included, and so meet a NaN exactly where
-        the reference's zero-padded conv does (ref path_embedding.py:48-51, :129-132) once the horizon is smeared in."""
-        if getattr(self, "_dirty_split", None) is None or self._dirty_split[0] != back:
-            flags = _native.rows_nonfinite(ds)
-            dirty_idx = torch.nonzero(flags).flatten()
-            clean_idx = torch.nonzero(flags == 0).flatten()
-            clean_rows = ds[clean_idx, 0, :].contiguous()
-            dirty_rows = _native.smear_nonfinite(ds[dirty_idx].contiguous(), back, 0) if dirty_idx.numel() else None
-            self._dirty_split = (back, clean_idx, clean_rows, dirty_idx, dirty_rows)
-        return self._dirty_split[1:]
-
     def _native_scan(self, x: torch.Tensor, y: torch.Tensor, k: int, defer_status: bool = False):
         """(d, idx, resident dataset) on the device.  `defer_status` (Identity scans only): ONE raw call, its status
         tensor returned as a fourth item instead of being waited for -- the caller reads it together with the results
@@ -364,8 +350,9 @@ class PathShadowing:
         dev = self._hip_device()
         _native.load()
         self._served_by = "hip"
+        kind = self._native_kind(x, y, k)
         ds = self._resident_dataset(y, dev)
-        rows = self._scan_rows_of(ds, smear=self._native_kind(x, y, k) not in ("linear", "padded"))
+        rows = self._scan_rows_of(ds, smear=kind not in ("linear", "padded"))
         h = self.context.get_out_times()
         if self._workspace is None or self._workspace.device != dev:
             self._workspace = _native.Workspace(dev)
@@ -373,153 +360,69 @@ class PathShadowing:
         if k > n_windows:
             # the reference fails inside torch.topk (ref :165) with the same exception type
             raise RuntimeError("selected index k out of range")
-        kind = self._native_kind(x, y, k)
         if kind in ("linear", "padded"):
-            # the (tiny) query embedding stays the module's own conv1d (ref :140); the scan
-            # over the ensemble takes the unpadded kernel and the horizon as an integer --
-            # or, for an ImputationContext, the kernel with the gap's zero taps and no horizon
-            ker = self.embedding.kernel
-            with single_thread():
-                hx = self.embedding(x.to(ker.device))[:, 0, :].contiguous()
-            hx = hx.to(dev)
-            back = h
-            if kind == "padded":
-                h = 0
-            # the scanning kernel on the device, kept while the module's kernel tensor is the same object at the same
-            # version (an in-place edit bumps it): no upload per call, and the library may keep what it found in the matrix
-            kkey = (id(ker), ker._version, kind, str(dev), tuple(self.context.portion) if kind == "padded" else None)
-            if getattr(self, "_ker_dev", None) is None or self._ker_dev[0] != kkey:
-                if kind == "padded":
-                    ker2 = self.context.pad_context(ker)[:, 0, :].contiguous().to(dev)
-                else:
-                    ker2 = ker[:, 0, :].contiguous().to(dev)
-                self._ker_dev = (kkey, ker2, ker)            # (ker: keeps the id alive)
-            ker2 = self._ker_dev[1]
-            # a kernel without Foveal's suffix structure (a filter bank, a user kernel): the rejection test on the
-            # matrix cores (the library cannot look at the matrix without a synchronisation: the caller says which it is)
-            fl = 0 if isinstance(self.embedding, Foveal) else _native.FLAG_EMBED_MX
+            return self._scan_embedded(x, ds, rows, k, h, kind, dev) + (ds,)
+        got = self._scan_identity(x, rows, k, h, dev, defer_status)
+        return got[:2] + (ds,) + got[2:]
 
-            def embedded_topk(rows_t, kk, keep_plan):
-                """(d, idx) of the kk best windows of `rows_t` per query: the sampled scan, the exhaustive one for queries
-                whose status asks for it (candidate slices overflowed: massive ties / adversarial data)."""
-                d, idx, status = _native.scan_topk_embedded(rows_t, ker2, hx, kk, h=h, workspace=self._workspace, flags=fl,
-                                                            keep_plan=keep_plan)
-                bad = torch.nonzero(status != _native.PSH_STATUS_OK).flatten()
-                if bad.numel():
-                    d2, idx2, _ = _native.scan_topk_embedded(rows_t, ker2, hx[bad].contiguous(), kk, h=h, workspace=self._workspace,
-                                                             exhaustive=True, flags=fl)
-                    d[bad] = d2
-                    idx[bad] = idx2
-                return d, idx
+    def _scan_embedded(self, x: torch.Tensor, ds: torch.Tensor, rows: torch.Tensor, k: int, h: int, kind: str, dev: torch.device):
+        """(d, idx) behind a linear embedding.  The (tiny) query embedding stays the module's own conv1d (ref :140); the scan
+        over the ensemble takes the unpadded kernel and the horizon as an integer -- or, for an ImputationContext ("padded"),
+        the kernel with the gap's zero taps and no horizon."""
+        ker = self.embedding.kernel
+        with single_thread():
+            hx = self.embedding(x.to(ker.device))[:, 0, :].contiguous()
+        hx = hx.to(dev)
+        back = h if kind == "linear" else 0
+        if kind == "padded":
+            h = 0
+        # the scanning kernel on the device, kept while the module's kernel tensor is the same object at the same
+        # version (an in-place edit bumps it): no upload per call, and the library may keep what it found in the matrix
+        kkey = (id(ker), ker._version, kind, str(dev), tuple(self.context.portion) if kind == "padded" else None)
+        if getattr(self, "_ker_dev", None) is None or self._ker_dev[0] != kkey:
+            ker2 = (self.context.pad_context(ker) if kind == "padded" else ker)[:, 0, :].contiguous().to(dev)
+            self._ker_dev = (kkey, ker2, ker)            # (ker: keeps the id alive)
+        ker2 = self._ker_dev[1]
+        # a kernel without Foveal's suffix structure (a filter bank, a user kernel): the rejection test on the
+        # matrix cores (the library cannot look at the matrix without a synchronisation: the caller says which it is)
+        fl = 0 if isinstance(self.embedding, Foveal) else _native.FLAG_EMBED_MX
+        one_window = rows.shape[-1] == ker2.shape[-1] + h
+        if self._dirty:
+            # NaN / +-inf in the ensemble: its rows split once per resident copy, the two parts scanned and merged (_dirty.py)
+            if self._dirty_split is None or self._dirty_split.back != back:
+                self._dirty_split = DirtyRows(ds, back)
+            return self._dirty_split.topk(hx, ker2, k, h, self._workspace, fl, one_window=one_window)
+        if one_window:
+            # ONE window per row: the reference's embedded view (S, 1, d) is contiguous and its distance the
+            # 8-lane reduce over d (ref path_embedding.py:129-132, path_distance.py:65) -- embed every row once,
+            # then scan R pre-embedded points (rows one window long): psh_embed_rows + psh_scan_topk
+            points = _native.embed_rows(rows.contiguous(), ker2)
+            return _native.scan_topk_checked(points, hx, k, h=0, workspace=self._workspace)
+        # (keep_plan: ker2 is the cached device copy above -- same tensor, same version = same matrix)
+        return _native.scan_topk_embedded_checked(rows, ker2, hx, k, h=h, workspace=self._workspace, flags=fl, keep_plan=True)
 
-            one_window = rows.shape[-1] == ker2.shape[-1] + h
-            if not self._dirty:
-                if one_window:
-                    # ONE window per row: the reference's embedded view (S, 1, d) is contiguous and its distance the
-                    # 8-lane reduce over d (ref path_embedding.py:129-132, path_distance.py:65) -- embed every row once,
-                    # then scan R pre-embedded points (rows one window long): psh_embed_rows + psh_scan_topk
-                    points = _native.embed_rows(rows.contiguous(), ker2)
-                    d, idx = _native.scan_topk_checked(points, hx, k, h=0, workspace=self._workspace)
-                    return d, idx, ds
-                # (keep_plan: ker2 is the cached device copy above -- same tensor, same version = same matrix)
-                d, idx = embedded_topk(rows, k, True)
-                return d, idx, ds
-            # ---- NaN / +-inf in the ensemble behind a linear embedding.  The reference's conv1d makes a window NaN when ANY tap
-            # of its zero-padded kernel meets one (0 * NaN); the native rejection tests assume finite data.  Rows without such a
-            # sample (almost all) are scanned as ever; the few that hold one go through the exhaustive dense chains on rows
-            # with the horizon smeared in (every tap multiplied: the conv's rule exactly); the two lists are merged by (d, r, t).
-            clean_idx, clean_rows, dirty_idx, dirty_rows = self._split_dirty_rows(ds, back if kind == "linear" else 0)
-            Tp = ds.shape[-1] - ker2.shape[-1] - h + 1
-            B_ = hx.shape[0]
-            parts_d, parts_i = [], []
-            n_clean, n_dirty = int(clean_idx.numel()) * Tp, int(dirty_idx.numel()) * Tp
-            if n_clean > 0:
-                kc = min(k, n_clean)
-                if one_window:
-                    points = _native.embed_rows(clean_rows, ker2)
-                    dc, ic = _native.scan_topk_checked(points, hx, kc, h=0, workspace=self._workspace)
-                elif kc == k:
-                    dc, ic = embedded_topk(clean_rows, kc, False)
-                else:
-                    dc, ic, _ = _native.scan_topk_embedded(clean_rows, ker2, hx, kc, h=h, workspace=self._workspace, exhaustive=True, flags=fl)
-                ic = ic.clone()
-                ic[..., 0] = clean_idx[ic[..., 0].long()].to(torch.int32)
-                parts_d.append(dc)
-                parts_i.append(ic)
-            if n_dirty > 0 and (n_clean < k or not one_window):
-                kd = min(k, n_dirty)
-                if one_window:
-                    # a dirty row IS its one window: NaN, ranked behind every clean one (ref :165)
-                    dd = torch.full((B_, kd), float("nan"), dtype=torch.float32, device=dev)
-                    idd = torch.zeros((B_, kd, 2), dtype=torch.int32, device=dev)
-                    idd[..., 0] = dirty_idx[:kd].to(torch.int32)[None, :]
-                else:
-                    # (EMBED_DENSE: every one of the K taps is multiplied, zeros included -- the suffix-rows walk would skip the
-                    #  taps in front of Foveal's longest row, where the conv still meets a NaN)
-                    dd, idd, _ = _native.scan_topk_embedded(dirty_rows, ker2, hx, kd, h=h, workspace=self._workspace, exhaustive=True,
-                                                            flags=_native.FLAG_EMBED_DENSE)
-                    idd = idd.clone()
-                    idd[..., 0] = dirty_idx[idd[..., 0].long()].to(torch.int32)
-                parts_d.append(dd)
-                parts_i.append(idd)
-            if len(parts_d) == 1 and parts_d[0].shape[1] == k:
-                return parts_d[0], parts_i[0], ds
-            d, idx = _native.merge_topk(torch.cat(parts_d, dim=1).contiguous(), torch.cat(parts_i, dim=1).contiguous(), k)
-            return d, idx, ds
-
-        # ---- Identity windows
-        # A batch's 8-bit rejection test (32 queries and more, W <= 25: psh_capi.hip) puts every query of a call on ONE
-        # quantisation step (include/psh.h, PSH_FLAG_MQ_F16): queries that differ in amplitude by more than ~3x go to the library
-        # as separate calls, one per amplitude class (a factor of 3 each) -- a call's time is proportional to its queries, so the
-        # classes cost what the batch would, plus a quarter of a millisecond of fixed work per class -- as long as every class
-        # keeps the 32 queries the 8-bit test wants.  Otherwise (small classes, small batches, longer windows: the f16 test) the
-        # classes are a factor of 64 wide.  Decided here, where the queries are still host memory.
+    def _scan_identity(self, x: torch.Tensor, rows: torch.Tensor, k: int, h: int, dev: torch.device, defer_status: bool):
+        """(d, idx) of the Identity scan -- (d, idx, status) of the raw calls with `defer_status`: one call, or one per amplitude
+        class of a batch whose queries are still host memory (amplitude_classes)."""
         classes, flags = None, 0
-        i8 = x.shape[0] >= 32 and x.shape[-1] <= 25            # the call would meet the 8-bit test
         if x.shape[0] > 1 and x.device.type == "cpu":
-            amp = x[:, 0, :].abs().amax(dim=1)
-            top = float(amp[torch.isfinite(amp)].max()) if bool(torch.isfinite(amp).any()) else 0.0
-            if top > 0.0 and not (top <= 3.0 * float(amp.min())):
-                def by_factor(f):
-                    cls = torch.floor(torch.log(torch.clamp(amp / top, min=1e-30)) / math.log(f) + 1e-6).to(torch.int64)
-                    cls = torch.where(torch.isfinite(amp) & (amp > 0), cls, torch.full_like(cls, -1000))   # zero / non-finite queries: a class of their own
-                    return [torch.nonzero(cls == c).flatten() for c in torch.unique(cls, sorted=True).tolist()[::-1]]
-                fine = by_factor(3.0)
-                if i8 and min(int(c.numel()) for c in fine) >= 32:
-                    classes = fine                                # every class keeps the 8-bit test
-                else:
-                    # the f16 test copes with amplitudes a few dozen times apart on its one scale (beyond that a quiet query
-                    # keeps more windows than its slices hold and falls to the exhaustive pass): classes a factor of 64 wide,
-                    # each ONE call, on the f16 test where the 8-bit one would have met more than its factor of 3
-                    classes = by_factor(64.0)
-                    flags = _native.FLAG_MQ_F16 if i8 else 0
-                if len(classes) == 1:
-                    classes = None
+            classes, flags = amplitude_classes(x[:, 0, :].abs().amax(dim=1), x.shape[-1])
+
+        def scan(xq):
+            fn = _native.scan_topk if defer_status else _native.scan_topk_checked
+            return fn(rows, xq.contiguous().to(dev), k, h=h, workspace=self._workspace, flags=flags)
+
         if classes is None:
-            xq = x[:, 0, :].contiguous().to(dev)
-            if defer_status:
-                d, idx, status = _native.scan_topk(rows, xq, k, h=h, workspace=self._workspace, flags=flags)
-                return d, idx, ds, status
-            d, idx = _native.scan_topk_checked(rows, xq, k, h=h, workspace=self._workspace, flags=flags)
-            return d, idx, ds
+            return scan(x[:, 0, :])
         B_ = x.shape[0]
-        d = torch.empty((B_, k), dtype=torch.float32, device=dev)
-        idx = torch.empty((B_, k, 2), dtype=torch.int32, device=dev)
-        status = torch.zeros(B_, dtype=torch.int32, device=dev)
+        whole = (torch.empty((B_, k), dtype=torch.float32, device=dev), torch.empty((B_, k, 2), dtype=torch.int32, device=dev),
+                 torch.zeros(B_, dtype=torch.int32, device=dev))
         for sel in classes:
-            xq = x[sel, 0, :].contiguous().to(dev)
+            # (deferred: no synchronisation per class -- the statuses travel with the results, the caller reads them once)
             sel_d = sel.to(dev)
-            if defer_status:
-                # (no synchronisation per class: the statuses travel with the results, the caller reads them once)
-                dc, ic, sc = _native.scan_topk(rows, xq, k, h=h, workspace=self._workspace, flags=flags)
-                status[sel_d] = sc
-            else:
-                dc, ic = _native.scan_topk_checked(rows, xq, k, h=h, workspace=self._workspace, flags=flags)
-            d[sel_d] = dc
-            idx[sel_d] = ic
-        if defer_status:
-            return d, idx, ds, status
-        return d, idx, ds
+            for t, part in zip(whole, scan(x[sel, 0, :])):
+                t[sel_d] = part
+        return whole if defer_status else whole[:2]
 
     @staticmethod
     def _to_host(*tensors: torch.Tensor) -> tuple[np.ndarray, ...]:
@@ -605,23 +508,8 @@ class PathShadowing:
             if got is not None:
                 return got
         if cuda and self._native_ok(x, y, k):
-            out = self._native_scan(x, y, k, defer_status=True)
-            self.last_path = self._served_by
-            if len(out) == 4:
-                # the status travels with the results: gather and copies are enqueued behind the scan unconditionally
-                # (a status other than OK -- the fused launch gave up, candidate slices overflowed -- is rare and then
-                # costs the wasted gather), one synchronisation for everything
-                d, idx, ds, status = out
-                paths = _native.gather_paths(ds, idx, length)
-                hd, hp, hi, hs = self._to_host(d, paths, idx, status)
-                if not hs.any():
-                    return hd, hp, hi
-                if bool((hs == _native.PSH_STATUS_RETRY).any()):
-                    self._workspace.arm()
-                out = self._native_scan(x, y, k)
-            d, idx, ds = out
-            paths = _native.gather_paths(ds, idx, length)           # (B, k, C, len) on device
-            return self._to_host(d, paths, idx)
+            # gather and copies are enqueued behind the scan, everything comes down with its status (_scan_then)
+            return self._scan_then(x, y, k, lambda d, idx, ds: (None, (d, _native.gather_paths(ds, idx, length), idx)))[1]
 
         d, idx = self._generic_scan(x, y, k, n_splits, cuda)
         self.last_path = "torch"
@@ -631,6 +519,25 @@ class PathShadowing:
         t = idx[..., 1].long()[..., None] + offs                     # (B, k, len)
         paths = y[r[..., None], :, t]                                # (B, k, len, C)
         return _numpy(d), _numpy(paths.permute(0, 1, 3, 2).contiguous()), _numpy(idx)
+
+    def _scan_then(self, x: torch.Tensor, y: torch.Tensor, k: int, consume: Callable):
+        """The native scan with its consumer behind it and ONE synchronisation: `consume(d, idx, ds)` enqueues its work on the
+        scan's device results and returns (what it keeps on the device, the device tensors to bring down); this returns (what it
+        kept, those tensors as numpy arrays).  An Identity scan's status travels with the results: the consumer is enqueued
+        unconditionally, and a status other than OK (the fused launch gave up, candidate slices overflowed: rare, and then the
+        consumer's work is wasted) means the checked scan and the consumer once more."""
+        out = self._native_scan(x, y, k, defer_status=True)
+        self.last_path = self._served_by
+        if len(out) == 4:
+            kept, down = consume(*out[:3])
+            *host, hs = self._to_host(*down, out[3])
+            if not hs.any():
+                return kept, tuple(host)
+            if bool((hs == _native.PSH_STATUS_RETRY).any()):
+                self._workspace.arm()
+            out = self._native_scan(x, y, k)
+        kept, down = consume(*out)
+        return kept, self._to_host(*down)
 
     def _shadow_prepared(self, x: torch.Tensor, y: torch.Tensor, k: int):
         """shadow() for ONE Identity query as one blocking library call (_native.BlockingShadow -> psh_shadow_blocking: the fused
@@ -836,24 +743,9 @@ class PathShadowing:
                 raise TypeError("device_predict: to_predict must map the (B, k, C, h) torch tensor of out-context paths to a "
                                 f"torch tensor (B, k, ...); got {type(values).__name__}"
                                 f"{tuple(getattr(values, 'shape', ()))}")
-            return values
+            return values, (d,)
 
-        out = self._native_scan(x, y, k, defer_status=True)
-        self.last_path = self._served_by
-        d_host = values = None
-        if len(out) == 4:                                   # Identity scan: the status is read with the results (see shadow())
-            d, idx, ds, status = out
-            values = evaluate(d, idx, ds)
-            d_host, hs = self._to_host(d, status)
-            if hs.any():
-                if bool((hs == _native.PSH_STATUS_RETRY).any()):
-                    self._workspace.arm()
-                d_host = None
-                out = self._native_scan(x, y, k)
-        if d_host is None:
-            d, idx, ds = out
-            values = evaluate(d, idx, ds)
-            (d_host,) = self._to_host(d)
+        values, (d_host,) = self._scan_then(x, y, k, evaluate)
         return values, d_host
 
     def _predict_on_device(self, x: torch.Tensor, y: torch.Tensor, k: int, to_predict: Callable,
@@ -894,41 +786,48 @@ class PathShadowing:
         `to_predict.accepts_torch = True`, as `shadowing.realized_variance` does -- evaluates `to_predict` on the
         device tensor instead, so the paths never leave HBM (_predict_on_device).  A numpy-style callable is NOT
         silently given tensors: `x.std(-1)` is Bessel-corrected in torch and not in numpy."""
+        if device_predict is None:
+            device_predict = bool(getattr(to_predict, "accepts_torch", False))
+
+        def on_host(xr):
+            d, paths, _ = self.shadow(xr, k, n_dataset_splits, cuda)
+            return self.predict_from_paths(d, paths, to_predict, proba_name, eta)
+
+        parts = self._over_context_splits(x_context, k, n_context_splits, cuda, device_predict, on_host,
+                                          lambda xr, y: self._predict_on_device(xr, y, k, to_predict, proba_name, eta), tqdm)
+        return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+
+    def _over_context_splits(self, x_context: ArrayType, k: int, n_context_splits: int, cuda: bool, device_wanted: bool,
+                             on_host: Callable, on_device: Callable, progress: Callable = iter) -> list:
+        """What predict(), predict_quantiles() and smile() share: the queries in `n_context_splits` batches (ref :286-301), each
+        served by `on_device(x, y)` when cuda=True, the caller wants it (`device_wanted`) and the batch is natively scanned,
+        by `on_host(x)` otherwise; the list of what they returned.  With cuda=True the batches of this ONE call share one upload
+        of a dataset that is otherwise re-read per call (`_predict_scope`: the array cannot change between them)."""
         x = _torch(_dim_array(x_context))
         n = x.shape[0]
         y = None
-        if device_predict is None:
-            device_predict = bool(getattr(to_predict, "accepts_torch", False))
-        means, stds = [], []
-        # (cuda=True: the context splits of this ONE call share one upload of a dataset that is otherwise re-read per call)
+        parts = []
         self._predict_scope = (self.dataset, None) if cuda else None
         try:
-            for rows in tqdm(torch.arange(n).split(n // n_context_splits)):
-                if cuda and device_predict:
+            for rows in progress(torch.arange(n).split(max(1, n // n_context_splits))):
+                xr = x[rows, ...]
+                if cuda and device_wanted:
                     y = self._dataset_tensor() if y is None else y
-                    if self._native_ok(x[rows, ...], y, k):
-                        got = self._predict_on_device(x[rows, ...], y, k, to_predict, proba_name, eta)
-                        means.append(got[0])
-                        stds.append(got[1])
+                    if self._native_ok(xr, y, k):
+                        parts.append(on_device(xr, y))
                         continue
-                d, paths, _ = self.shadow(x[rows, ...], k, n_dataset_splits, cuda)
-                m, s = self.predict_from_paths(d, paths, to_predict, proba_name, eta)
-                means.append(m)
-                stds.append(s)
+                parts.append(on_host(xr))
         finally:
             if self._predict_scope is not None and self._predict_scope[1] is not None:
                 self._scan_rows = self._dirty_split = None          # (they keep the per-call upload alive)
             self._predict_scope = None
-        return np.concatenate(means), np.concatenate(stds)
+        return parts
 
     # ------------------------------------------------------------------ predictive quantiles (README "Predictive quantiles")
     def _quantile_weights(self, proba_name: str, distances: np.ndarray, eta: float | None):
         """The (B, k) weights of the installed averaging class (None: unit weights), as smile() takes them.  A class that
         does not expose `weights` cannot weigh a quantile: nothing of it is restated here."""
-        proba = self.init_averaging_proba(proba_name, distances, eta)
-        if not hasattr(proba, "weights"):
-            raise TypeError(f"{type(proba).__name__} exposes no `weights`: weighted quantiles need the weights themselves")
-        return self._smile_weights(proba_name, distances, eta)
+        return averaging_weights(self.init_averaging_proba(proba_name, distances, eta), *distances.shape)
 
     def quantiles_from_paths(self, distances: np.ndarray, paths, to_predict: Callable, levels,
                              proba_name: str = "softmax", eta: float | None = None):
@@ -949,31 +848,23 @@ class PathShadowing:
         distances come down, the weights go up, and only the three (B, Q, ...) results come back
         (`last_quantile_reduction` says "device" or "host")."""
         from .quantiles import PredictiveQuantiles, weighted_quantiles
-        x = _torch(_dim_array(x_context))
-        n = x.shape[0]
-        y = None
         if device_predict is None:
             device_predict = bool(getattr(to_predict, "accepts_torch", False))
-        parts = []
-        self._predict_scope = (self.dataset, None) if cuda else None
-        try:
-            for rows in torch.arange(n).split(max(1, n // n_context_splits)):
-                if cuda and device_predict and k <= _native.PSH_MAX_K:
-                    y = self._dataset_tensor() if y is None else y
-                    if self._native_ok(x[rows, ...], y, k):
-                        values, d_host = self._scan_and_evaluate(x[rows, ...], y, k, to_predict)
-                        w = self._quantile_weights(proba_name, d_host, eta)
-                        on_device = values.is_cuda and values.dtype == torch.float32
-                        self.last_quantile_reduction = "device" if on_device else "host"
-                        parts.append(weighted_quantiles(values, w, levels, cuda=on_device))
-                        continue
-                d, paths, _ = self.shadow(x[rows, ...], k, n_dataset_splits, cuda)
-                self.last_quantile_reduction = "host"
-                parts.append(self.quantiles_from_paths(d, paths, to_predict, levels, proba_name, eta))
-        finally:
-            if self._predict_scope is not None and self._predict_scope[1] is not None:
-                self._scan_rows = self._dirty_split = None          # (they keep the per-call upload alive)
-            self._predict_scope = None
+
+        def on_host(xr):
+            d, paths, _ = self.shadow(xr, k, n_dataset_splits, cuda)
+            self.last_quantile_reduction = "host"
+            return self.quantiles_from_paths(d, paths, to_predict, levels, proba_name, eta)
+
+        def on_device(xr, y):
+            values, d_host = self._scan_and_evaluate(xr, y, k, to_predict)
+            w = self._quantile_weights(proba_name, d_host, eta)
+            on_dev = values.is_cuda and values.dtype == torch.float32
+            self.last_quantile_reduction = "device" if on_dev else "host"
+            return weighted_quantiles(values, w, levels, cuda=on_dev)
+
+        parts = self._over_context_splits(x_context, k, n_context_splits, cuda, device_predict and k <= _native.PSH_MAX_K,
+                                          on_host, on_device)
         cat = lambda name: np.concatenate([getattr(p, name) for p in parts])   # noqa: E731
         return PredictiveQuantiles(parts[0].levels, cat("q"), cat("lower"), cat("upper"), cat("status"))
 
@@ -981,13 +872,7 @@ class PathShadowing:
     def _smile_weights(self, proba_name: str, distances: np.ndarray, eta: float | None):
         """(B, k) float64 weights of the installed averaging class for these distances, or None for uniform ones."""
         proba = self.init_averaging_proba(proba_name, distances, eta)
-        w = getattr(proba, "weights", None)
-        if w is None:
-            return None
-        w = np.asarray(w, dtype=np.float64)
-        while w.ndim > 2 and w.shape[-1] == 1:
-            w = w[..., 0]
-        return np.ascontiguousarray(np.broadcast_to(w, distances.shape), dtype=np.float64)
+        return averaging_weights(proba, *distances.shape) if hasattr(proba, "weights") else None
 
     def smile_from_paths(self, distances: np.ndarray, paths, Ts, Ms, proba_name: str = "softmax", eta: float | None = None,
                          r: float = 0.0, x_init: float = 100.0, channel: int = 0, degree: int = 3, kind: str = "otm",
@@ -1017,29 +902,62 @@ class PathShadowing:
         from .pricing import concat_smiles, smile_from_log_returns
         if not isinstance(self.context, PredictionContext):
             raise NotImplementedError("smile: only a PredictionContext has an out-context to price on")
-        x = _torch(_dim_array(x_context))
-        n = x.shape[0]
-        y = None
-        parts = []
-        for rows in torch.arange(n).split(max(1, n // n_context_splits)):
-            xr = x[rows, ...]
-            if cuda and k <= _native.PSH_MAX_K:
-                y = self._dataset_tensor() if y is None else y
-                if self._native_ok(xr, y, k):
-                    d, idx, ds = self._native_scan(xr, y, k)
-                    self.last_path = self._served_by
-                    W = xr.shape[-1]
-                    paths = _native.gather_paths(ds, idx, W + self.context.get_out_times())
-                    (d_host,) = self._to_host(d)
-                    w = self._smile_weights(proba_name, d_host, eta)
-                    wt = None if w is None else torch.from_numpy(w.copy()).to(paths.device)
-                    future = self.context.select_out_context(paths)[:, :, channel, :]
-                    parts.append(smile_from_log_returns(future, wt, Ts, Ms, x_init, r, degree=degree, kind=kind, cuda=True,
-                                                        report=report))
-                    continue
+
+        def on_host(xr):
             d, paths, _ = self.shadow(xr, k, n_dataset_splits, cuda)
-            parts.append(self.smile_from_paths(d, paths, Ts, Ms, proba_name, eta, r, x_init, channel, degree, kind, report))
-        return concat_smiles(parts)
+            return self.smile_from_paths(d, paths, Ts, Ms, proba_name, eta, r, x_init, channel, degree, kind, report)
+
+        def on_device(xr, y):
+            future, d_host = self._scan_and_evaluate(xr, y, k, lambda out_context: out_context[:, :, channel, :])
+            w = self._smile_weights(proba_name, d_host, eta)
+            wt = None if w is None else torch.from_numpy(w.copy()).to(future.device)
+            return smile_from_log_returns(future, wt, Ts, Ms, x_init, r, degree=degree, kind=kind, cuda=True, report=report)
+
+        return concat_smiles(self._over_context_splits(x_context, k, n_context_splits, cuda, k <= _native.PSH_MAX_K,
+                                                       on_host, on_device))
+
+
+def amplitude_classes(amp: torch.Tensor, W: int):
+    """How a batch of Identity queries with the largest |sample|s `amp` (B,) and windows of W samples goes to the library:
+    (classes, flags) -- a list of index tensors that partition range(B), one call each, or None for one call; `flags` for
+    every call.
+    A batch's 8-bit rejection test (32 queries and more, W <= 25: psh_capi.hip) puts every query of a call on ONE quantisation
+    step (include/psh.h, PSH_FLAG_MQ_F16): queries that differ in amplitude by more than ~3x go as separate calls, one per
+    amplitude class (a factor of 3 each) -- a call's time is proportional to its queries, so the classes cost what the batch
+    would, plus a quarter of a millisecond of fixed work per class -- as long as every class keeps the 32 queries the 8-bit test
+    wants.  Otherwise (small classes, small batches, longer windows: the f16 test) the classes are a factor of 64 wide: the f16
+    test copes with amplitudes a few dozen times apart on its one scale (beyond that a quiet query keeps more windows than its
+    slices hold and falls to the exhaustive pass), each ONE call, on the f16 test where the 8-bit one would have met more than
+    its factor of 3.  Zero and non-finite queries form a class of their own, last."""
+    i8 = amp.shape[0] >= 32 and W <= 25                    # the call would meet the 8-bit test
+    finite = torch.isfinite(amp)
+    top = float(amp[finite].max()) if bool(finite.any()) else 0.0
+    if not top > 0.0 or top <= 3.0 * float(amp.min()):
+        return None, 0
+
+    def by_factor(f):
+        cls = torch.floor(torch.log(torch.clamp(amp / top, min=1e-30)) / math.log(f) + 1e-6).to(torch.int64)
+        cls = torch.where(finite & (amp > 0), cls, torch.full_like(cls, -1000))
+        return [torch.nonzero(cls == c).flatten() for c in torch.unique(cls, sorted=True).tolist()[::-1]]
+
+    classes, flags = by_factor(3.0), 0
+    if not (i8 and min(int(c.numel()) for c in classes) >= 32):
+        classes, flags = by_factor(64.0), (_native.FLAG_MQ_F16 if i8 else 0)
+    return (classes if len(classes) > 1 else None), flags
+
+
+def averaging_weights(proba, B: int, k: int):
+    """The (B, k) float64 C-contiguous weights an averaging object exposes (trailing unit axes dropped, broadcast), or None
+    for uniform ones; TypeError when it exposes no `weights` -- nothing of the class is restated here."""
+    if not hasattr(proba, "weights"):
+        raise TypeError(f"{type(proba).__name__} exposes no `weights`: weighted quantiles need the weights themselves")
+    w = proba.weights
+    if w is None:
+        return None
+    w = np.asarray(w, dtype=np.float64)
+    while w.ndim > 2 and w.shape[-1] == 1:
+        w = w[..., 0]
+    return np.ascontiguousarray(np.broadcast_to(w, (B, k)))
 
 
 _MOMENT_CLASSES: dict = {}      # averaging class -> its avg / std ARE the weighted moments of its `weights` (probed once)
@@ -1050,19 +968,12 @@ def moment_weights(proba, B: int, k: int):
     sum_j w_j x_j and sqrt(sum_j w_j (x_j - mean)^2) of those weights: True for uniform weights 1/k, an array otherwise,
     None when the object does not expose weights or when ITS OWN avg / std disagree with the moments on a probe (then the
     caller lets the object reduce on the host: the class is the authority, nothing of it is restated)."""
-    if not hasattr(proba, "weights"):
+    try:
+        if proba.weights is not None and np.shape(proba.weights)[:2] != (B, k):
+            return None                                      # (nothing is broadcast here: such a class reduces on the host itself)
+        w = averaging_weights(proba, B, k)
+    except Exception:  # noqa: BLE001
         return None
-    w = proba.weights
-    if w is not None:
-        try:
-            w = np.asarray(w, dtype=np.float64)
-        except Exception:  # noqa: BLE001
-            return None
-        while w.ndim > 2 and w.shape[-1] == 1:
-            w = w[..., 0]
-        if w.shape != (B, k):
-            return None
-        w = np.ascontiguousarray(w)
     verdict = _MOMENT_CLASSES.get(type(proba))               # the probe below runs once per averaging CLASS
     if verdict is not None:
         return (True if w is None else w) if verdict else None
