@@ -821,6 +821,7 @@ static int try_stream_step(const Call& c, const Problem& p, const Workspace& w, 
     void* cand_list = nullptr;
     stream_cand_list(w, B, &cand_list, &cand_cap);
     const int tile_fl = mx_tile_floats(p.W);
+    // (copy_scan_kernel's LDS -- copy_scan_shmem_bytes -- is stream_scan_kernel's less 64 KB: where the fp32 scan fits, it fits)
     if (!((one_long ? stream_scan_long_shmem_bytes(p.W, B) : stream_scan_shmem_bytes_q(tile_fl, B)) <= PSH_LDS_BYTES &&
           ((units_p >= 256 && r2p <= units_p / 2) || rt.hint) &&
           5 * (int64_t)p.k <= (int64_t)cand_cap && 5 * (int64_t)p.k * B <= grid_s * front * 2))

@@ -52,7 +52,7 @@
 // read and not an unbounded gather.
 //
 // The audit.  Every survivor has its fp32 samples at hand: (f16)(y 2^e_c) is computed again and compared bit for bit with
-// what the copy holds (deferred: the copy's halves from memory; staged: the scaled halves the test ran on, in LDS).  A
+// what the copy holds (its halves from memory, deferred or staged alike: the segment was just streamed, the lines are in L2).  A
 // mismatch -- the copy is of other data than the ensemble -- sets StreamCtl::ovf: the ranking reports PSH_STATUS_RETRY and the
 // caller reruns through the separate launches and drops the copy.  Only survivors are audited: a copy of another ensemble is
 // caught at once, a sparse edit the caller hid from the copy's owner may not be.
@@ -168,21 +168,40 @@ hipError_t launch_filter_copy_build(const float* ds, long long R, long long T, v
 // ------------------------------------------------------------------------------------------------------------------
 // S on the copy: stream_scan_kernel's place in the three launches (one query, W <= 33)
 // ------------------------------------------------------------------------------------------------------------------
-struct CStage {  // one segment of halves in flight: 3 x 16 bytes per lane (two sets per wave: 24 registers)
-    u32x4v v[3];
+struct CStage {  // one unit in flight: its four A fragments, 4 x 16 bytes per lane (two sets per wave: 32 registers)
+    u32x4v v[4];
 };
 enum { CS_FRONT = 0, CS_NEXT = 1 };
 
-// The LDS of a block is stream_scan_kernel's (stream_scan_shmem_bytes): 64 control words, the block's list, a 4.5 KB fp32 tile
-// and the two f16 arrays per wave -- and 8 KB for the eight B fragments (band of ones, shifted query), block-shared and read
-// per use: with both in registers and two stage sets the kernel spilled at 112 (155 KB: a sample block's 4.5 KB still fits
-// beside it; 20 KB of LDS traffic a unit against the 27 of stream_scan_kernel, whose fp32 tile store is gone).  The tile holds the wave's queue of deferred survivors; a dense segment's fp32 samples
-// take it over (the queue is verified first).  112 registers, like the scan it replaces: a sample or ranking wave of another
-// stream's step still fits beside four of these on a SIMD.
-// Stage sets: a segment is 2.1 KB here, so a wave owns TWO of them: while one is converted and its reload is issued the other's
-// unit is in flight.  Measured (profiles/filter_copy_bench.txt): 66 us a step against the fp32 scan's 88, a launch alone on the
-// chip 67 us = 4.0 TB/s where the bytes alone promise 45 -- and a third set (36 registers, no spill) measured the same, so it
-// is not the bytes in flight that hold the kernel now but what a unit costs in LDS traffic and issue slots.
+// Fragments from memory.  The copy's halves lie in memory exactly as an A fragment of the banded product wants them: row m of A
+// is the 64 halves [32 m, 32 m + 64) of the segment, and lane (m = lane & 31, hk = lane >> 5) holds, for K-step s, the eight
+// halves [32 m + 16 s + 8 hk, + 8) -- ONE 16-byte load (see `load`).  A unit is therefore four loads per lane, scaled by 2^delta
+// and squared with packed f16 multiplies in registers: nothing of a segment passes through LDS.  (Until this was so the
+// halves were staged as 16-byte pieces and written, with their squares, into two f16 arrays per wave, read back as fragments:
+// 6 ds_write_b128 + 8 ds_read_b128 a unit beside the 8 for the B fragments, 42 % of the launch's cycles with the LDS array
+// busy -- profiles/copy_scan_fragments.txt.)
+// The halves beyond the segment's last window.  Row 31 of A ends at half seg_start + 1055; the segment's windows end at
+// seg_start + PSH_SEG + W - 2.  The 33 - W halves in between are real halves of the row now -- the next segment's first
+// samples, or the row's zero tail (the staged arrays held zeros there).  They only meet zero taps of B: finite values add exact
+// zeros and every sum is what it was.  A NaN there (a non-finite sample, or one out of f16's range), and a value whose square
+// overflows f16 (inf x 0), poisons the accumulators of windows 992 .. 1023 of the segment: the NaN-safe compare KEEPS those
+// windows, the exact fp32 chain decides them, and no result changes -- every difference runs towards keeping
+// (tests/test_gpu_copy_scan_fragments.py).
+// The loads carry no cache hint.  The four loads of a unit ask for every 128-byte line of the segment from four instructions in
+// a row (a lane's 16 bytes are 64 bytes from its neighbour's): the vector L1 merges them while the line is in flight, and the L2
+// sees FEWER requests than from the pieces (2.14 M a launch against 2.41 M, FETCH_SIZE unchanged).  With the non-temporal hint
+// the piece loads had, the L1 keeps no line: 8.7 M requests and 29 % more bytes fetched, 101 us a step against 66; the hint on
+// some of the four, and K-steps 2 and 3 taken from lane m + 1 by DPP instead of loaded, all measured slower than four plain loads.
+// The LDS of a block: 64 control words, the block's list, a 4.5 KB fp32 tile per wave and 8 KB for the eight B fragments (band of
+// ones, shifted query), block-shared and read per use -- 8 ds_read_b128 a unit, all the LDS traffic a unit has left; with them in
+// registers two stage sets spill at 112.  81 KB, where stream_scan_kernel takes 146.  The tile holds the wave's queue of deferred
+// survivors; a dense segment's fp32 samples take it over (the queue is verified first).  At most 112 registers, like the scan
+// it replaces: a sample or ranking wave of another stream's step still fits beside four of these on a SIMD.
+// Stage sets: a wave owns TWO (32 registers): while one unit is scaled, squared and its set reloaded, the other's is in flight.
+// Measured (profiles/copy_scan_fragments.txt): 51.6 us a step (51.4 - 51.7) against the staged halves' 66.0 (65.5 - 66.1), every run
+// faster than the fastest of those; a launch alone on the chip 51.1 us against 65.8 = 5.3 TB/s of the 6.29 a copy kernel reaches,
+// consecutive steps' scans start 50.2 us apart; the LDS array is busy 13.7 % of the launch's cycles (42.5 %); the same bytes
+// (FETCH_SIZE 132935 KiB a launch) and exactly the same windows kept.
 // The sets take turns in a loop body spelled out twice, every load unconditional: see the loop.
 template <int WT>
 __global__ __launch_bounds__(PSH_SCAN_THREADS) __attribute__((amdgpu_num_vgpr(56))) void copy_scan_kernel(ScanArgs a, FusedArgs f, CopyArgs cp) {
@@ -199,29 +218,27 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) __attribute__((amdgpu_num_vgpr(56
     float* tiles = reinterpret_cast<float*>(fl + NFL);
     float* tile = tiles + (size_t)wave * a.tile_floats;
     u64* sq = reinterpret_cast<u64*>(tile);                                   // deferred survivors: row | t << 32
-    _Float16* ah0 = reinterpret_cast<_Float16*>(tiles + (size_t)NW * a.tile_floats);
-    _Float16* a1 = ah0 + (size_t)wave * 2 * PSH_MX_NHALF;                     // y^
-    _Float16* a2 = a1 + PSH_MX_NHALF;                                         // (y^2)^
-    _Float16* bol = ah0 + (size_t)NW * 2 * PSH_MX_NHALF;                      // the band of ones' four fragments, block-shared (4 KB)
+    _Float16* bol = reinterpret_cast<_Float16*>(tiles + (size_t)NW * a.tile_floats);   // the band of ones' four fragments, block-shared (4 KB)
     FusedHdr* hdr = f.hdr;
     const StreamCtl* sc = &hdr->stream;
 
     const int W = WT > 0 ? WT : a.W;
     const int nhalf = PSH_SEG + W - 1;
-    const int nch = (nhalf + 7) >> 3;                                         // 16-byte pieces of a segment: 129 .. 132
     const UnitQueue uq = unit_queue((unsigned)a.n_rows * (unsigned)a.nseg, &ctl[CS_NEXT]);
-    // A unit's three loads are issued whatever the unit: one past the block's share reads the copy's header instead, and the
-    // lanes beyond the segment's last piece read that piece again -- straight-line code, so that the wait in front of a stage set's
-    // use counts exactly the loads of the OTHER set that may stay in flight (behind a branch it would wait for all of them)
+    // The A fragment of K-step s for lane (m = lane & 31, hk = lane >> 5) is the eight halves [32 m + 16 s + 8 hk, + 8) of the
+    // segment (mx_load_a's rule): in the copy ONE 16-byte aligned load -- the header is 64 bytes, the pitch a multiple of 32 halves,
+    // a segment starts at a multiple of 1024 -- and the highest half touched, seg_start + 1055, lies inside the row (the pitch).
+    // A unit's four loads are issued whatever the unit: one past the block's share reads the copy's header instead, every lane at
+    // offset 0 -- straight-line code, so that the wait in front of a stage set's use counts exactly the loads of the OTHER set
+    // that may stay in flight (behind a branch it would wait for all of them)
+    const int frag0 = 32 * (lane & 31) + 8 * (lane >> 5);
     auto load = [&](CStage& st, unsigned uu) __attribute__((always_inline)) {
         const bool on = uu < uq.hi;
         const Unit c = unit_decode(a, on ? uu : uq.lo);
-        const u32x4v* src = on ? reinterpret_cast<const u32x4v*>(cp.rows + c.row(a) * cp.pitch + c.seg_start())
-                               : reinterpret_cast<const u32x4v*>(cp.hdr);
-        const int m0 = on ? lane : 0, m2 = on ? (lane + 128 < nch ? lane + 128 : nch - 1) : 0;
-        st.v[0] = __builtin_nontemporal_load(src + m0);
-        st.v[1] = __builtin_nontemporal_load(src + m0 + (on ? 64 : 0));
-        st.v[2] = __builtin_nontemporal_load(src + m2);
+        const unsigned short* src = on ? cp.rows + c.row(a) * cp.pitch + c.seg_start() + frag0
+                                       : reinterpret_cast<const unsigned short*>(cp.hdr);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) st.v[s] = *reinterpret_cast<const u32x4v*>(src + (on ? 16 * s : 0));
     };
     // the first two units of every wave are requested before anything else (static; the queue starts behind them)
     CStage s0, s1;
@@ -243,7 +260,6 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) __attribute__((amdgpu_num_vgpr(56
     int ec = cp.hdr->e_c;
     ec = ec < -60 ? -60 : (ec > 60 ? 60 : ec);
     if (first) { ctl[CS_FRONT] = 0; ctl[CS_NEXT] = 2 * NW; }
-    mx_zero(a1, lane);
     if (wave == 0) {                                                          // (window energies: arithmetic only)
         f16x8 bo[4];
         mx_band_ones(bo, W, lane);
@@ -323,33 +339,26 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) __attribute__((amdgpu_num_vgpr(56
         wave_lds_fence();                                                     // (the queue is read: it may be written again)
         qn = 0;
     };
-    // one unit: the staged halves -> the two f16 arrays, the next unit's request, the eight MFMAs, the survivors
+    // one unit: the staged fragments scaled and squared in registers, the next unit's request, the eight MFMAs, the survivors
     auto process = [&](CStage& st, unsigned u) __attribute__((always_inline)) -> unsigned {
         const bool on = u < uq.hi;                                            // (see the loop below)
         const Unit c = unit_decode(a, on ? u : uq.lo);
         const int seg_start = c.seg_start();
         const long long row = c.row(a);
+        f16x8 fa[4], fb[4];
 #pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            const int m = lane + 64 * q;
-            if (q < 2 || m < nch) {
-                const f16x8 v = __builtin_bit_cast(f16x8, st.v[q]) * hd;
-                *reinterpret_cast<f16x8*>(a1 + mx_half(8 * m)) = v;
-                *reinterpret_cast<f16x8*>(a2 + mx_half(8 * m)) = v * v;
-            }
+        for (int s = 0; s < 4; ++s) {
+            fb[s] = __builtin_bit_cast(f16x8, st.v[s]) * hd;                  // y^
+            fa[s] = fb[s] * fb[s];                                            // (y^2)^
         }
-        wave_lds_fence();
         const unsigned un = uq.grab(lane);
         load(st, un);
 
-        f16x8 fa[4];
         f32x16 acc;
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
-        mx_load_a(fa, a2, lane);
         acc = mx_mac4(fa, [&](int s) { return *reinterpret_cast<const f16x8*>(bop + (size_t)s * 64 * 8); }, acc);
-        mx_load_a(fa, a1, lane);
-        const f32x16 aq = mx_mac4(fa, [&](int s) { return *reinterpret_cast<const f16x8*>(bop + (size_t)(4 + s) * 64 * 8); }, acc);
+        const f32x16 aq = mx_mac4(fb, [&](int s) { return *reinterpret_cast<const f16x8*>(bop + (size_t)(4 + s) * 64 * 8); }, acc);
         if (on && mx_any_keep(aq, thr2)) {
             const unsigned hm = mx_keep_mask(aq, thr2);
             int n = 0;                                                        // survivors of the segment (uniform)
@@ -364,6 +373,7 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) __attribute__((amdgpu_num_vgpr(56
                 // a dense segment: its fp32 samples into the tile (the queue lives there: verified first), the chains from LDS
                 if (qn > 0) verify_queue();
                 const float* yrow = a.dataset + row * a.T;
+                const unsigned short* hrow = cp.rows + row * cp.pitch + seg_start;
                 const int lastf = (int)(a.T - seg_start) - 1;                 // (clamped tail: only inadmissible windows see it)
                 int ln = lane;
                 asm volatile("" : "+v"(ln));                                  // (this branch's addresses are made here, not kept across the unit loop)
@@ -379,11 +389,8 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) __attribute__((amdgpu_num_vgpr(56
                     bool stale = false;
                     if (keep) {
                         v = exact_one_rt(tile, p, x, Wr);                     // (the same chain as exact_one<W>; a rare branch: compact code)
-                        // the audit: the halves the test ran on against the samples' own encoding, scaled alike
-                        for (int j = 0; j < Wr; ++j) {
-                            const _Float16 e = __builtin_bit_cast(_Float16, copy_encode(tile[lds_pad(p + j)], sc_c)) * hd;
-                            stale = stale || __builtin_bit_cast(unsigned short, e) != __builtin_bit_cast(unsigned short, a1[mx_half(p + j)]);
-                        }
+                        // the audit: the samples' own encoding against the copy's halves (the segment was just streamed: L2)
+                        for (int j = 0; j < Wr; ++j) stale = stale || copy_encode(tile[lds_pad(p + j)], sc_c) != hrow[p + j];
                     }
                     give_up(stale);
                     admit_hits(keep && (v < tau2), v, (int)(row + a.r_offset), seg_start + p);
@@ -402,9 +409,9 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) __attribute__((amdgpu_num_vgpr(56
                     }
                     qn += (int)__popcll(mask);
                 }
+                wave_lds_fence();                                             // (verify_queue reads other lanes' entries)
             }
         }
-        wave_lds_fence();  // all lanes done with the arrays before they are overwritten
         return un;
     };
     // The two stage sets take turns, ALWAYS both: a set whose unit lies past the block's share (the last turns of a wave) holds the
@@ -441,8 +448,11 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) __attribute__((amdgpu_num_vgpr(56
     }
 }
 
-// stream_scan_kernel's LDS and 8 KB: the B fragments -- band of ones, shifted query -- sit in LDS instead of 32 registers
-size_t copy_scan_shmem_bytes(int tile_floats) { return stream_scan_shmem_bytes(tile_floats) + 2 * 4 * 64 * 8 * sizeof(_Float16); }
+// stream_scan_kernel's LDS without its two f16 arrays per wave (the A fragments come from memory), and 8 KB: the B fragments --
+// band of ones, shifted query -- sit in LDS instead of 32 registers
+size_t copy_scan_shmem_bytes(int tile_floats) {
+    return stream_scan_shmem_bytes(tile_floats) - (size_t)(PSH_SCAN_THREADS / 64) * 2 * PSH_MX_NHALF * sizeof(_Float16) + 2 * 4 * 64 * 8 * sizeof(_Float16);
+}
 
 hipError_t launch_copy_scan(const ScanArgs& a, const FusedArgs& f, const CopyArgs& cp, int grid, hipStream_t s) {
     const size_t shmem = copy_scan_shmem_bytes(a.tile_floats);
