@@ -577,6 +577,43 @@ int psh_weighted_quantiles(int device, void* stream, const float* values, const 
                            int32_t* out_status);
 
 /*
+ * Scores of weighted predictive ensembles against what happened: the CRPS (continuous ranked probability score), the PIT
+ * (probability integral transform: the predictive CDF at the outcome) and the mean, for a grid of weightings in one call.
+ * One column is one (b, i) of values (device B x k x m float32); y = obs[b, i] (device B x m float32) is the realised
+ * statistic.  Weight set e of query b is weights[e, b, 0 .. k-1] (device n_sets x B x k float64, AS GIVEN, never
+ * renormalised), or NULL: one set, w_j = 1.  n_sets <= PSH_SCORE_MAX_SETS.  For one column and one set, keep the paths with
+ * w > 0, order them by (value ascending, path index ascending), write x_(0..n-1), w_(i) for the sorted values and weights;
+ * all arithmetic is in double and the float32 values are converted exactly:
+ *   C_i = sum_{l<=i} w_(l)     S_i = sum_{l<=i} w_(l) x_(l)     W = C_{n-1} (as computed)
+ *   out_mean   = S_{n-1} / W
+ *   out_pit_lo = (sum of w_(i) with x_(i) <  y) / W          F(y-)
+ *   out_pit_hi = (sum of w_(i) with x_(i) <= y) / W          F(y)
+ *   c_i        = min(max(y, x_(i)), x_(i+1))
+ *   out_crps   = (x_(0) - y)_+ + (y - x_(n-1))_+
+ *                + (1 / W^2) sum_{i=0}^{n-2} [ C_i^2 (c_i - x_(i)) + (W - C_i)^2 (x_(i+1) - c_i) ]
+ * out_crps is the integral of (F(z) - 1[z >= y])^2 gap by gap, every term non-negative; it equals E|X - y| - 1/2 E|X - X'|
+ * under p = w / W.  out_crps, out_pit_lo, out_pit_hi, out_mean: device n_sets x B x m float64;  out_status: device
+ * n_sets x B int32 (PSH_SCORE_STATUS_* bits), zeroed by the call, or NULL.  A path of weight exactly 0 contributes nothing,
+ * whatever its value.  A non-finite value at a positive weight: the column's four results are NaN for that set,
+ * PSH_SCORE_STATUS_NONFINITE.  A non-finite or negative weight, or W not > 0: all of (e, b) is NaN, PSH_SCORE_STATUS_WEIGHTS
+ * (the values are then not looked at).  A non-finite obs[b, i]: the column is NaN for every set, PSH_SCORE_STATUS_OBS in
+ * every status[e, b].  -0.0 and +0.0 are one value.  So crps >= 0; n = 1 gives |x - y|; pit_lo <= pit_hi, equal unless a
+ * weighted path equals y.  No floating-point atomics: two calls give identical bits, so do weights scaled by a power of two
+ * (while W^2 neither overflows nor underflows), and a set's results do not depend on which other sets ride the call.
+ * A NULL values, obs or double output, B, k, m or n_sets < 1, n_sets > PSH_SCORE_MAX_SETS, or weights == NULL with
+ * n_sets != 1: PSH_ERR_ARG before anything touches the device; k > PSH_MAX_K or B * m >= 2^31: PSH_ERR_UNSUPPORTED.
+ * The method heads shadowing_amd/csrc/psh_scoring.hip; shadowing_amd/scoring.py is its numpy twin.
+ */
+#define PSH_SCORE_MAX_SETS 64
+#define PSH_SCORE_STATUS_OK         0
+#define PSH_SCORE_STATUS_NONFINITE  1   /* a path with positive weight has a non-finite value in some column */
+#define PSH_SCORE_STATUS_WEIGHTS    2   /* a non-finite or negative weight, or a weight sum that is not > 0 */
+#define PSH_SCORE_STATUS_OBS        4   /* a non-finite observation in some column of the query */
+int psh_score_ensemble(int device, void* stream, const float* values, const double* weights, const float* obs,
+                       int B, int k, int m, int n_sets,
+                       double* out_crps, double* out_pit_lo, double* out_pit_hi, double* out_mean, int32_t* out_status);
+
+/*
  * Hedged Monte Carlo (Potters, Bouchaud, Sestovic 2001) on the k shadowing paths of each of B dates: the option prices,
  * Black-Scholes implied vols and strikes of a smile.  The method, in full, heads shadowing_amd/csrc/psh_hmc.hip (and
  * README "Option pricing"); shadowing_amd/pricing.py is its numpy twin.

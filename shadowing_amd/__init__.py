@@ -16,6 +16,7 @@ from .mrw import (MRWGenerator, SMRWGenerator, mrw_log_returns, smrw_kernel, smr
 from .pdv import AutoregressiveLinearPredictor, PDVModel, PDVModelDiscrete
 from .pricing import HedgedPnL, HedgePolicy, PriceData, Smile, compute_smile, hedge_pnl
 from .quantiles import PredictiveQuantiles, weighted_quantiles
+from .scoring import EnsembleScore, score_ensemble
 from .statistics import realized_variance
 from .stylized import LaggedMoments, fit_smrw, lagged_moments
 from .scattering import (ScatteringSpectra, scattering_bank, scattering_generate, scattering_loss, scattering_spectra,
@@ -30,6 +31,6 @@ __all__ = [
     "MRWGenerator", "mrw_log_returns", "SMRWGenerator", "smrw_log_returns", "smrw_kernel", "smrw_leverage",
     "smrw_sq_moment", "LaggedMoments", "lagged_moments", "fit_smrw",
     "ScatteringSpectra", "scattering_spectra", "scattering_bank", "scattering_sums", "scattering_loss",
-    "scattering_generate", "PredictiveQuantiles", "weighted_quantiles",
+    "scattering_generate", "PredictiveQuantiles", "weighted_quantiles", "EnsembleScore", "score_ensemble",
 ]
 __version__ = "0.1.0"

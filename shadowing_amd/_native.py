@@ -62,7 +62,7 @@ EXPORTS = ("psh_version", "psh_strerror", "psh_last_hip_error", "psh_workspace_b
            "psh_hedge_replay_workspace_bytes", "psh_hedge_replay", "psh_pdv_generate", "psh_mrw_generate", "psh_smrw_generate",
            "psh_lagged_moments", "psh_lagged_moments_workspace_bytes", "psh_scattering_spectra",
            "psh_scattering_spectra_workspace_bytes", "psh_scattering_vjp", "psh_scattering_vjp_workspace_bytes",
-           "psh_weighted_quantiles", "psh_filter_copy_bytes", "psh_filter_copy_build", "psh_scan_topk_copy")
+           "psh_weighted_quantiles", "psh_score_ensemble", "psh_filter_copy_bytes", "psh_filter_copy_build", "psh_scan_topk_copy")
 
 _lib = None
 
@@ -168,6 +168,8 @@ def load() -> C.CDLL:
     L.psh_weighted_moments.argtypes = [i32, vp, vp, vp, i32, i32, i32, vp, vp]
     L.psh_weighted_quantiles.restype = i32
     L.psh_weighted_quantiles.argtypes = [i32, vp, vp, vp, i32, i32, i32, C.POINTER(C.c_double), i32, vp, vp, vp, vp]
+    L.psh_score_ensemble.restype = i32
+    L.psh_score_ensemble.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     L.psh_realized_variance.restype = i32
     L.psh_realized_variance.argtypes = [i32, vp, vp, i64, i64, i32, C.POINTER(C.c_int), i32, i32, vp]
     L.psh_hedged_mc.restype = i32
@@ -1139,6 +1141,39 @@ def weighted_quantiles(values: torch.Tensor, weights: torch.Tensor | None, level
                                          q.data_ptr(), lower.data_ptr(), upper.data_ptr(), status.data_ptr()),
            "psh_weighted_quantiles")
     return q, lower, upper, status
+
+
+PSH_SCORE_MAX_SETS = 64
+PSH_SCORE_STATUS_OK, PSH_SCORE_STATUS_NONFINITE, PSH_SCORE_STATUS_WEIGHTS, PSH_SCORE_STATUS_OBS = 0, 1, 2, 4
+
+
+def score_ensemble(values: torch.Tensor, weights: torch.Tensor | None, obs: torch.Tensor):
+    """psh_score_ensemble over axis 1 of a (B, k, ...) float32 statistic against the (B, ...) float32 observations, under
+    (E, B, k) float64 weight sets (None: one set of unit weights): (crps, pit_lo, pit_hi, mean), each (E, B, ...) float64,
+    and status (E, B) int32, all on the device; nothing is synchronised here."""
+    v = _dev_tensor(values, torch.float32, "values")
+    if v.dim() < 2:
+        raise ValueError("values must be (B, k, ...)")
+    B, k = v.shape[:2]
+    m = v.numel() // (B * k) if B * k else 0
+    if m == 0:
+        raise ValueError("values is empty")
+    y = _dev_tensor(obs, torch.float32, "obs")
+    if tuple(y.shape) != (B,) + tuple(v.shape[2:]):
+        raise ValueError(f"obs must be {(B,) + tuple(v.shape[2:])}, got {tuple(y.shape)}")
+    E, w_ptr = 1, None
+    if weights is not None:
+        w = _dev_tensor(weights, torch.float64, "weights")
+        if w.dim() != 3 or tuple(w.shape[1:]) != (B, k):
+            raise ValueError(f"weights must be (E, B, k) with (B, k) = ({B}, {k}), got {tuple(w.shape)}")
+        E, w_ptr = int(w.shape[0]), w.data_ptr()
+    shape = (E, B) + tuple(v.shape[2:])
+    crps, pit_lo, pit_hi, mean = (torch.empty(shape, dtype=torch.float64, device=v.device) for _ in range(4))
+    status = torch.empty((E, B), dtype=torch.int32, device=v.device)
+    _check(load().psh_score_ensemble(v.device.index, _stream_ptr(v.device), v.data_ptr(), w_ptr, y.data_ptr(), B, k, m, E,
+                                     crps.data_ptr(), pit_lo.data_ptr(), pit_hi.data_ptr(), mean.data_ptr(),
+                                     status.data_ptr()), "psh_score_ensemble")
+    return crps, pit_lo, pit_hi, mean, status
 
 
 def _uniform_rows(x: torch.Tensor):

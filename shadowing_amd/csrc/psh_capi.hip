@@ -1510,6 +1510,22 @@ int psh_weighted_quantiles(int device, void* stream, const float* values, const 
     return PSH_OK;
 }
 
+int psh_score_ensemble(int device, void* stream, const float* values, const double* weights, const float* obs, int B, int k,
+                       int m, int n_sets, double* out_crps, double* out_pit_lo, double* out_pit_hi, double* out_mean,
+                       int32_t* out_status) {
+    if (!values || !obs || !out_crps || !out_pit_lo || !out_pit_hi || !out_mean || B <= 0 || k <= 0 || m <= 0 || n_sets <= 0 ||
+        n_sets > PSH_SCORE_MAX_SETS || (!weights && n_sets != 1))
+        return PSH_ERR_ARG;
+    if (k > PSH_MAX_K || (int64_t)B * m >= ((int64_t)1 << 31)) return PSH_ERR_UNSUPPORTED;   // (one workgroup per column)
+    ScoreArgs a{};
+    a.values = values; a.weights = weights; a.obs = obs; a.B = B; a.k = k; a.m = m; a.n_sets = n_sets;
+    a.crps = out_crps; a.pit_lo = out_pit_lo; a.pit_hi = out_pit_hi; a.mean = out_mean; a.status = out_status;
+    GUARD_DEVICE(device);
+    if (out_status) HIP_TRY(hipMemsetAsync(out_status, 0, (size_t)n_sets * B * sizeof(int32_t), (hipStream_t)stream));
+    HIP_TRY(launch_score(a, (hipStream_t)stream));
+    return PSH_OK;
+}
+
 // the argument checks and the launch arguments that psh_hedged_mc and psh_hedged_mc_policy share
 static int hmc_fill_args(HmcArgs& a, const float* dlnx, int64_t row_stride, int B, int k, int len, const double* weights,
                          double x_init, double rate, const int* Ts, int nT, const double* Ms, int nM, int degree, int kind,

@@ -416,6 +416,21 @@ struct QuantileArgs {
 };
 hipError_t launch_quantiles(const QuantileArgs& a, hipStream_t s);
 
+// psh_scoring.hip: CRPS, PIT and mean of the k paths against an observation, for every weight set (psh_score_ensemble)
+struct ScoreArgs {
+    const float* values;      // (B, k, m)
+    const double* weights;    // (n_sets, B, k), or nullptr: one set, w = 1
+    const float* obs;         // (B, m)
+    int B, k, m, n_sets;
+    int sets_per_group;       // set by the launcher: the sets one workgroup serves
+    double* crps;             // (n_sets, B, m), as pit_lo, pit_hi and mean
+    double* pit_lo;
+    double* pit_hi;
+    double* mean;
+    int32_t* status;          // (n_sets, B), zeroed by the caller, or nullptr
+};
+hipError_t launch_score(const ScoreArgs& a, hipStream_t s);
+
 // psh_hmc.hip: hedged Monte Carlo on the shadowing paths of a date (psh_hedged_mc)
 #define PSH_HMC_SG 3              // strikes a block solves (the Gram matrix of a step is shared by them)
 #define PSH_HMC_MAX_T 64

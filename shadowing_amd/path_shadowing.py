@@ -145,6 +145,7 @@ class PathShadowing:
         self.last_path = None       # "hip" / "torch": which implementation served the last shadow() / predict()
         self.last_predict_reduction = None   # device_predict: "device" (psh_weighted_moments) / "host" (the class's own avg / std)
         self.last_quantile_reduction = None  # predict_quantiles: "device" (psh_weighted_quantiles) / "host" (the numpy twin)
+        self.last_score_reduction = None     # score: "device" (psh_score_ensemble) / "host" (the numpy twin)
 
     @staticmethod
     def _load_with_scatspectra(dataset):
@@ -867,6 +868,93 @@ class PathShadowing:
                                           on_host, on_device)
         cat = lambda name: np.concatenate([getattr(p, name) for p in parts])   # noqa: E731
         return PredictiveQuantiles(parts[0].levels, cat("q"), cat("lower"), cat("upper"), cat("status"))
+
+    # ------------------------------------------------------------------ scoring (README "Scoring the predictions")
+    def _score_weights(self, proba_name: str, distances: np.ndarray, etas, ks):
+        """The (len(etas) * len(ks), B, k) float64 weight sets of a grid: set (eta, k') holds the installed averaging class's
+        own weights for the k' smallest distances of each query (stable argsort; shadow() returns them ascending) and 0 for
+        the other k - k' paths.  Returns (weights, etas, ks)."""
+        from .scoring import MAX_SETS
+        d = np.asarray(distances, dtype=np.float64)
+        B, k = d.shape
+        etas = tuple(etas)
+        ks = (k,) if ks is None else tuple(int(n) for n in ks)
+        if not etas or not ks:
+            raise ValueError("score: etas and ks must not be empty")
+        if len(etas) * len(ks) > MAX_SETS:
+            raise ValueError(f"score: {len(etas)} etas x {len(ks)} ks = {len(etas) * len(ks)} weight sets, at most {MAX_SETS} a call")
+        if min(ks) < 1 or max(ks) > k:
+            raise ValueError(f"score: every k' must lie in 1 .. k = {k}, got {list(ks)}")
+        order = np.argsort(d, axis=1, kind="stable")
+        w = np.zeros((len(etas), len(ks), B, k))
+        for a, eta in enumerate(etas):
+            for c, kc in enumerate(ks):
+                near = order[:, :kc]
+                wk = averaging_weights(self.init_averaging_proba(proba_name, np.take_along_axis(d, near, axis=1), eta), B, kc)
+                np.put_along_axis(w[a, c], near, 1.0 if wk is None else wk, axis=1)
+        return w.reshape(len(etas) * len(ks), B, k), etas, ks
+
+    def _observe(self, x_realized, to_predict: Callable, device=None):
+        """The realised statistic (B, ...): `to_predict` sees the realised out-context (B, C, h) as it sees the paths', one
+        path a query."""
+        xr = _dim_array(x_realized)
+        xr = _torch(xr).to(device)[:, None] if device is not None else _numpy(xr)[:, None]
+        return to_predict(xr)[:, 0]
+
+    @staticmethod
+    def _grid_score(score, etas, ks):
+        from .scoring import EnsembleScore
+        grid = (len(etas), len(ks))
+        return EnsembleScore(*(getattr(score, n).reshape(grid + getattr(score, n).shape[1:])
+                               for n in ("crps", "pit_lo", "pit_hi", "mean", "status")), etas, ks)
+
+    def score_from_paths(self, distances: np.ndarray, paths, x_realized, to_predict: Callable, etas, ks=None,
+                         proba_name: str = "softmax"):
+        """CRPS, PIT and mean of `to_predict(out-context)` over the k paths against `to_predict` of what followed each query,
+        `x_realized` (B, C, h), for every pair of an eta in `etas` (None entries as in init_averaging_proba) and a cut-off
+        k' <= k in `ks` (default [k]): a scoring.EnsembleScore whose set axis is (len(etas), len(ks)).  Numpy paths take the
+        numpy twin, HIP tensors psh_score_ensemble."""
+        from .scoring import score_ensemble
+        values = to_predict(self.context.select_out_context(paths))
+        d = distances.detach().cpu().numpy() if isinstance(distances, torch.Tensor) else np.asarray(distances)
+        w, etas, ks = self._score_weights(proba_name, d, etas, ks)
+        on_dev = isinstance(values, torch.Tensor) and values.is_cuda
+        obs = self._observe(x_realized, to_predict, values.device if on_dev else None)
+        return self._grid_score(score_ensemble(values, w, obs), etas, ks)
+
+    def score(self, x_context: ArrayType, x_realized: ArrayType, k: int, to_predict: Callable, etas, ks=None,
+              proba_name: str = "softmax", n_dataset_splits: int = 1, n_context_splits: int = 1,
+              cuda: bool = False, device_predict: bool | None = None):
+        """shadow() + score_from_paths() over `n_context_splits` batches of queries, with predict()'s opt-in rule for
+        `device_predict`.  With cuda=True, device_predict=True on a natively scanned configuration with k <= PSH_MAX_K the
+        scan runs once, the paths and the statistic stay in HBM: the (B, k) distances come down, the (E, B, k) weights of
+        the grid go up, and only the four (E, B, ...) results come back (`last_score_reduction` says "device" or "host")."""
+        from .scoring import EnsembleScore, score_ensemble
+        if device_predict is None:
+            device_predict = bool(getattr(to_predict, "accepts_torch", False))
+        xr_all = _torch(_dim_array(x_realized))
+        n = xr_all.shape[0]
+        if n != _dim_array(x_context).shape[0]:
+            raise ValueError(f"score: {_dim_array(x_context).shape[0]} queries but {n} realised futures")
+        batches = iter(xr_all.split(max(1, n // n_context_splits)))     # the batches of _over_context_splits, in its order
+
+        def on_host(xr):
+            d, paths, _ = self.shadow(xr, k, n_dataset_splits, cuda)
+            self.last_score_reduction = "host"
+            return self.score_from_paths(d, paths, _numpy(next(batches)), to_predict, etas, ks, proba_name)
+
+        def on_device(xr, y):
+            values, d_host = self._scan_and_evaluate(xr, y, k, to_predict)
+            w, es, kk = self._score_weights(proba_name, d_host, etas, ks)
+            on_dev = values.is_cuda and values.dtype == torch.float32
+            self.last_score_reduction = "device" if on_dev else "host"
+            obs = self._observe(next(batches), to_predict, values.device)
+            return self._grid_score(score_ensemble(values, w, obs, cuda=on_dev), es, kk)
+
+        parts = self._over_context_splits(x_context, k, n_context_splits, cuda, device_predict and k <= _native.PSH_MAX_K,
+                                          on_host, on_device)
+        cat = lambda name: np.concatenate([getattr(p, name) for p in parts], axis=2)   # noqa: E731
+        return EnsembleScore(cat("crps"), cat("pit_lo"), cat("pit_hi"), cat("mean"), cat("status"), parts[0].etas, parts[0].ks)
 
     # ------------------------------------------------------------------ option pricing (README "Option pricing")
     def _smile_weights(self, proba_name: str, distances: np.ndarray, eta: float | None):
