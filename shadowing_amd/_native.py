@@ -51,18 +51,76 @@ class PshFilterCopy(C.Structure):
                 ("served", C.c_int), ("reason", C.c_int)]
 
 
-EXPORTS = ("psh_version", "psh_strerror", "psh_last_hip_error", "psh_workspace_bytes", "psh_query_norm",
-           "psh_scan_topk", "psh_scan_topk_exhaustive", "psh_scan_topk_embedded",
-           "psh_scan_topk_embedded_exhaustive", "psh_merge_workspace_bytes", "psh_merge_topk",
-           "psh_merge_topk_gathered", "psh_merge_sorted_gathered", "psh_gather_paths", "psh_embed_rows",
-           "psh_embedded_supported", "psh_embed_plan_offset", "psh_candidates_layout", "psh_workspace_init", "psh_last_comm_error", "psh_comm_unique_id", "psh_comm_create",
-           "psh_comm_destroy", "psh_comm_world", "psh_exchange_merge", "psh_stream_create_reserving", "psh_stream_destroy",
-           "psh_weighted_moments", "psh_realized_variance", "psh_count_nonfinite", "psh_smear_nonfinite", "psh_rows_nonfinite",
-           "psh_shadow_block_layout", "psh_shadow_blocking", "psh_hedged_mc", "psh_hmc_policy_doubles", "psh_hedged_mc_policy",
-           "psh_hedge_replay_workspace_bytes", "psh_hedge_replay", "psh_pdv_generate", "psh_mrw_generate", "psh_smrw_generate",
-           "psh_lagged_moments", "psh_lagged_moments_workspace_bytes", "psh_scattering_spectra",
-           "psh_scattering_spectra_workspace_bytes", "psh_scattering_vjp", "psh_scattering_vjp_workspace_bytes",
-           "psh_weighted_quantiles", "psh_score_ensemble", "psh_filter_copy_bytes", "psh_filter_copy_build", "psh_scan_topk_copy")
+def _signatures() -> dict:
+    """The argument types of every entry point include/psh.h declares, by name (tests/test_capi_abi_cpu.py holds the
+    table against the header's prototypes)."""
+    vp, i64, i32, f64, u64, sz, P = C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_uint64, C.c_size_t, C.POINTER
+    scan_args = [i32, vp, vp, i64, i64, i64, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, P(PshProfile)]
+    emb_args = [i32, vp, vp, i64, i64, i64, vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, P(PshProfile)]
+    hmc_args = [i32, vp, vp, i64, i32, i32, i32, vp, f64, f64, P(i32), i32, P(f64), i32, i32, i32]
+    hedged_mc = hmc_args + [vp, vp, vp, vp, vp]
+    return {
+        "psh_version": [],
+        "psh_strerror": [i32],
+        "psh_last_hip_error": [],
+        "psh_workspace_bytes": [i64, i64, i32, i32, i32, i32, P(sz)],
+        "psh_workspace_init": [i32, vp, vp, sz],
+        "psh_query_norm": [i32, vp, vp, i32, i32, vp],
+        "psh_scan_topk": scan_args,
+        "psh_scan_topk_exhaustive": scan_args,
+        "psh_scan_topk_copy": scan_args + [P(PshFilterCopy)],
+        "psh_filter_copy_bytes": [i64, i64, P(sz), P(i64)],
+        "psh_filter_copy_build": [i32, vp, vp, i64, i64, vp, sz, vp, sz],
+        "psh_scan_topk_embedded": emb_args,
+        "psh_scan_topk_embedded_exhaustive": emb_args,
+        "psh_embedded_supported": [i32, i32],
+        "psh_embed_plan_offset": [],
+        "psh_embed_rows": [i32, vp, vp, i64, i64, vp, i32, i32, vp],
+        "psh_candidates_layout": [i64, i64, i32, i32, i32, i32, sz, P(i64)],
+        "psh_merge_workspace_bytes": [i32, i32, P(sz)],
+        "psh_merge_topk": [i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, sz],
+        "psh_merge_topk_gathered": [i32, vp, vp, vp, i32, i64, i64, i32, i32, i32, vp, vp, vp, sz],
+        "psh_merge_sorted_gathered": [i32, vp, vp, vp, i32, i64, i64, i32, i32, i32, vp, vp],
+        "psh_gather_paths": [i32, vp, vp, i64, i64, i64, i64, vp, i64, i32, vp],
+        "psh_last_comm_error": [],
+        "psh_comm_unique_id": [C.c_char_p, vp],
+        "psh_comm_create": [C.c_char_p, i32, i32, i32, vp, P(vp)],
+        "psh_comm_destroy": [vp],
+        "psh_comm_world": [vp],
+        "psh_exchange_merge": [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, sz, vp, vp],
+        "psh_stream_create_reserving": [i32, i32, P(vp), P(i32)],
+        "psh_stream_destroy": [i32, vp],
+        "psh_shadow_block_layout": [i32, i32, i32, i64, P(sz)],
+        "psh_shadow_blocking": [i32, vp, vp, i64, i64, i64, vp, i64, i32, i32, i32, vp, sz, i32, vp, sz, P(PshProfile)],
+        "psh_count_nonfinite": [i32, vp, vp, i64, vp],
+        "psh_rows_nonfinite": [i32, vp, vp, i64, i64, i64, vp],
+        "psh_smear_nonfinite": [i32, vp, vp, i64, i64, i64, i32, i32, vp],
+        "psh_weighted_moments": [i32, vp, vp, vp, i32, i32, i32, vp, vp],
+        "psh_weighted_quantiles": [i32, vp, vp, vp, i32, i32, i32, P(f64), i32, vp, vp, vp, vp],
+        "psh_score_ensemble": [i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
+        "psh_realized_variance": [i32, vp, vp, i64, i64, i32, P(i32), i32, i32, vp],
+        "psh_hedged_mc": hedged_mc,
+        "psh_hedged_mc_policy": hedged_mc + [vp],
+        "psh_hmc_policy_doubles": [i32, i32, i32, i32, i32, P(sz)],
+        "psh_hedge_replay_workspace_bytes": [i32, i32, i32, i32, P(sz)],
+        "psh_hedge_replay": hmc_args + [vp, vp, vp, vp, vp, vp, vp, sz],
+        "psh_pdv_generate": [i32, vp, i32, i64, i32] + [P(f64)] * 6 + [i32, f64, f64, f64, vp, vp, vp, u64, vp, vp, vp, vp, vp],
+        "psh_mrw_generate": [i32, vp, i64, i32, f64, vp, vp, f64, u64, vp, i64, vp, vp],
+        "psh_smrw_generate": [i32, vp, i64, i32, i32, f64, vp, vp, f64, f64, u64, vp, i64, vp, vp],
+        "psh_lagged_moments_workspace_bytes": [i64, i32, i64, P(sz)],
+        "psh_lagged_moments": [i32, vp, vp, i64, i64, i32, i32, i64, vp, vp, vp, vp, sz],
+        "psh_scattering_spectra_workspace_bytes": [i64, i32, i64, P(sz)],
+        "psh_scattering_spectra": [i32, vp, vp, i64, i64, i32, i32, vp, i64, vp, vp, vp, vp, sz],
+        "psh_scattering_vjp_workspace_bytes": [i64, i32, i32, i64, P(sz)],
+        "psh_scattering_vjp": [i32, vp, vp, i64, i64, i32, i32, vp, i64, vp, vp, i64, vp, vp, sz],
+    }
+
+
+SIGNATURES = _signatures()
+# every entry point returns int (a PSH_* code), but:
+RESTYPES = {"psh_strerror": C.c_char_p, "psh_last_hip_error": C.c_char_p, "psh_last_comm_error": C.c_char_p,
+            "psh_embed_plan_offset": C.c_size_t}
+EXPORTS = tuple(SIGNATURES)
 
 _lib = None
 
@@ -93,120 +151,9 @@ def load() -> C.CDLL:
         L = C.CDLL(str(path))
     except OSError as e:  # pragma: no cover
         raise NativeLibraryError(f"cannot load {path}: {e}") from e
-    vp, i64, i32 = C.c_void_p, C.c_int64, C.c_int
-    L.psh_version.restype = i32
-    L.psh_strerror.restype = C.c_char_p
-    L.psh_strerror.argtypes = [i32]
-    L.psh_last_hip_error.restype = C.c_char_p
-    L.psh_workspace_bytes.restype = i32
-    L.psh_workspace_bytes.argtypes = [i64, i64, i32, i32, i32, i32, C.POINTER(C.c_size_t)]
-    L.psh_last_comm_error.restype = C.c_char_p
-    L.psh_comm_unique_id.restype = i32
-    L.psh_comm_unique_id.argtypes = [C.c_char_p, vp]
-    L.psh_comm_create.restype = i32
-    L.psh_comm_create.argtypes = [C.c_char_p, i32, i32, i32, vp, C.POINTER(vp)]
-    L.psh_comm_destroy.restype = i32
-    L.psh_comm_destroy.argtypes = [vp]
-    L.psh_comm_world.restype = i32
-    L.psh_comm_world.argtypes = [vp]
-    L.psh_exchange_merge.restype = i32
-    L.psh_exchange_merge.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, C.c_size_t, vp, vp]
-    L.psh_stream_create_reserving.restype = i32
-    L.psh_stream_create_reserving.argtypes = [i32, i32, C.POINTER(vp), C.POINTER(i32)]
-    L.psh_stream_destroy.restype = i32
-    L.psh_stream_destroy.argtypes = [i32, vp]
-    L.psh_workspace_init.restype = i32
-    L.psh_workspace_init.argtypes = [i32, vp, vp, C.c_size_t]
-    L.psh_query_norm.restype = i32
-    L.psh_query_norm.argtypes = [i32, vp, vp, i32, i32, vp]
-    scan_args = [i32, vp, vp, i64, i64, i64, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, C.c_size_t,
-                 C.POINTER(PshProfile)]
-    L.psh_scan_topk.restype = i32
-    L.psh_scan_topk.argtypes = scan_args
-    L.psh_scan_topk_exhaustive.restype = i32
-    L.psh_scan_topk_exhaustive.argtypes = scan_args
-    L.psh_scan_topk_copy.restype = i32
-    L.psh_scan_topk_copy.argtypes = scan_args + [C.POINTER(PshFilterCopy)]
-    L.psh_filter_copy_bytes.restype = i32
-    L.psh_filter_copy_bytes.argtypes = [i64, i64, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]
-    L.psh_filter_copy_build.restype = i32
-    L.psh_filter_copy_build.argtypes = [i32, vp, vp, i64, i64, vp, C.c_size_t, vp, C.c_size_t]
-    emb_args = [i32, vp, vp, i64, i64, i64, vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, C.c_size_t,
-                C.POINTER(PshProfile)]
-    L.psh_scan_topk_embedded.restype = i32
-    L.psh_scan_topk_embedded.argtypes = emb_args
-    L.psh_scan_topk_embedded_exhaustive.restype = i32
-    L.psh_scan_topk_embedded_exhaustive.argtypes = emb_args
-    L.psh_merge_workspace_bytes.restype = i32
-    L.psh_merge_workspace_bytes.argtypes = [i32, i32, C.POINTER(C.c_size_t)]
-    L.psh_merge_topk.restype = i32
-    L.psh_merge_topk.argtypes = [i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, C.c_size_t]
-    L.psh_merge_topk_gathered.restype = i32
-    L.psh_merge_topk_gathered.argtypes = [i32, vp, vp, vp, i32, i64, i64, i32, i32, i32, vp, vp, vp, C.c_size_t]
-    L.psh_merge_sorted_gathered.restype = i32
-    L.psh_merge_sorted_gathered.argtypes = [i32, vp, vp, vp, i32, i64, i64, i32, i32, i32, vp, vp]
-    L.psh_embed_plan_offset.restype = C.c_size_t
-    L.psh_embed_plan_offset.argtypes = []
-    L.psh_candidates_layout.restype = i32
-    L.psh_candidates_layout.argtypes = [i64, i64, i32, i32, i32, i32, C.c_size_t, C.POINTER(C.c_int64)]
-    L.psh_embedded_supported.restype = i32
-    L.psh_embedded_supported.argtypes = [i32, i32]
-    L.psh_embed_rows.restype = i32
-    L.psh_embed_rows.argtypes = [i32, vp, vp, i64, i64, vp, i32, i32, vp]
-    L.psh_count_nonfinite.restype = i32
-    L.psh_count_nonfinite.argtypes = [i32, vp, vp, i64, vp]
-    L.psh_shadow_block_layout.restype = i32
-    L.psh_shadow_block_layout.argtypes = [i32, i32, i32, i64, C.POINTER(C.c_size_t)]
-    L.psh_shadow_blocking.restype = i32
-    L.psh_shadow_blocking.argtypes = [i32, vp, vp, i64, i64, i64, vp, i64, i32, i32, i32, vp, C.c_size_t, i32, vp, C.c_size_t,
-                                      C.POINTER(PshProfile)]
-    L.psh_rows_nonfinite.restype = i32
-    L.psh_rows_nonfinite.argtypes = [i32, vp, vp, i64, i64, i64, vp]
-    L.psh_smear_nonfinite.restype = i32
-    L.psh_smear_nonfinite.argtypes = [i32, vp, vp, i64, i64, i64, i32, i32, vp]
-    L.psh_weighted_moments.restype = i32
-    L.psh_weighted_moments.argtypes = [i32, vp, vp, vp, i32, i32, i32, vp, vp]
-    L.psh_weighted_quantiles.restype = i32
-    L.psh_weighted_quantiles.argtypes = [i32, vp, vp, vp, i32, i32, i32, C.POINTER(C.c_double), i32, vp, vp, vp, vp]
-    L.psh_score_ensemble.restype = i32
-    L.psh_score_ensemble.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
-    L.psh_realized_variance.restype = i32
-    L.psh_realized_variance.argtypes = [i32, vp, vp, i64, i64, i32, C.POINTER(C.c_int), i32, i32, vp]
-    L.psh_hedged_mc.restype = i32
-    L.psh_hedged_mc.argtypes = [i32, vp, vp, i64, i32, i32, i32, vp, C.c_double, C.c_double, C.POINTER(C.c_int), i32,
-                                C.POINTER(C.c_double), i32, i32, i32, vp, vp, vp, vp, vp]
-    L.psh_hedged_mc_policy.restype = i32
-    L.psh_hedged_mc_policy.argtypes = L.psh_hedged_mc.argtypes + [vp]
-    L.psh_hmc_policy_doubles.restype = i32
-    L.psh_hmc_policy_doubles.argtypes = [i32, i32, i32, i32, i32, C.POINTER(C.c_size_t)]
-    L.psh_hedge_replay_workspace_bytes.restype = i32
-    L.psh_hedge_replay_workspace_bytes.argtypes = [i32, i32, i32, i32, C.POINTER(C.c_size_t)]
-    L.psh_hedge_replay.restype = i32
-    L.psh_hedge_replay.argtypes = [i32, vp, vp, i64, i32, i32, i32, vp, C.c_double, C.c_double, C.POINTER(C.c_int), i32,
-                                   C.POINTER(C.c_double), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, C.c_size_t]
-    L.psh_pdv_generate.restype = i32
-    L.psh_pdv_generate.argtypes = [i32, vp, i32, i64, i32] + [C.POINTER(C.c_double)] * 6 + [i32, C.c_double, C.c_double,
-                                                                                          C.c_double, vp, vp, vp, C.c_uint64,
-                                                                                          vp, vp, vp, vp, vp]
-    L.psh_mrw_generate.restype = i32
-    L.psh_mrw_generate.argtypes = [i32, vp, i64, i32, C.c_double, vp, vp, C.c_double, C.c_uint64, vp, i64, vp, vp]
-    L.psh_smrw_generate.restype = i32
-    L.psh_smrw_generate.argtypes = [i32, vp, i64, i32, i32, C.c_double, vp, vp, C.c_double, C.c_double, C.c_uint64, vp, i64,
-                                    vp, vp]
-    L.psh_lagged_moments_workspace_bytes.restype = i32
-    L.psh_lagged_moments_workspace_bytes.argtypes = [i64, i32, i64, C.POINTER(C.c_size_t)]
-    L.psh_lagged_moments.restype = i32
-    L.psh_lagged_moments.argtypes = [i32, vp, vp, i64, i64, i32, i32, i64, vp, vp, vp, vp, C.c_size_t]
-    L.psh_scattering_spectra_workspace_bytes.restype = i32
-    L.psh_scattering_spectra_workspace_bytes.argtypes = [i64, i32, i64, C.POINTER(C.c_size_t)]
-    L.psh_scattering_spectra.restype = i32
-    L.psh_scattering_spectra.argtypes = [i32, vp, vp, i64, i64, i32, i32, vp, i64, vp, vp, vp, vp, C.c_size_t]
-    L.psh_scattering_vjp_workspace_bytes.restype = i32
-    L.psh_scattering_vjp_workspace_bytes.argtypes = [i64, i32, i32, i64, C.POINTER(C.c_size_t)]
-    L.psh_scattering_vjp.restype = i32
-    L.psh_scattering_vjp.argtypes = [i32, vp, vp, i64, i64, i32, i32, vp, i64, vp, vp, i64, vp, vp, C.c_size_t]
-    L.psh_gather_paths.restype = i32
-    L.psh_gather_paths.argtypes = [i32, vp, vp, i64, i64, i64, i64, vp, i64, i32, vp]
+    for name, argtypes in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = RESTYPES.get(name, C.c_int), argtypes
     if L.psh_version() != PSH_VERSION:
         raise NativeLibraryError(f"{path} speaks version {L.psh_version()} of the C ABI, this binding version {PSH_VERSION} "
                                  "(psh_profile differs): rebuild it with `python -m shadowing_amd._build`")
@@ -243,10 +190,23 @@ def _stream_ptr(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
-def workspace_bytes(R: int, T: int, B: int, W: int, h: int, k: int) -> int:
+def _ptr(t: torch.Tensor | None):
+    return None if t is None else t.data_ptr()
+
+
+def _workspace_bytes(bytes_fn, *sizes) -> int:
     out = C.c_size_t(0)
-    _check(load().psh_workspace_bytes(R, T, B, W, h, k, C.byref(out)), "psh_workspace_bytes")
-    return int(out.value)
+    _check(bytes_fn(*sizes, C.byref(out)), bytes_fn.__name__)
+    return out.value
+
+
+def _workspace(bytes_fn, *sizes, device) -> torch.Tensor:
+    """The workspace an entry point asks for through its *_workspace_bytes companion, as int64 words on `device`."""
+    return torch.empty((max(_workspace_bytes(bytes_fn, *sizes), 8) + 7) // 8, dtype=torch.int64, device=device)
+
+
+def workspace_bytes(R: int, T: int, B: int, W: int, h: int, k: int) -> int:
+    return _workspace_bytes(load().psh_workspace_bytes, R, T, B, W, h, k)
 
 
 class Workspace:
@@ -1011,9 +971,7 @@ def merge_topk(d_lists: torch.Tensor, idx_lists: torch.Tensor, k: int):
     B, n = d.shape
     if tuple(ix.shape) != (B, n, 2):
         raise ValueError("idx_lists must be (B, n, 2)")
-    need = C.c_size_t(0)
-    _check(load().psh_merge_workspace_bytes(B, k, C.byref(need)), "psh_merge_workspace_bytes")
-    ws = torch.empty(int(need.value), dtype=torch.uint8, device=d.device)
+    ws = torch.empty(merge_workspace_bytes(B, k), dtype=torch.uint8, device=d.device)
     out_d = torch.empty((B, k), dtype=torch.float32, device=d.device)
     out_idx = torch.empty((B, k, 2), dtype=torch.int32, device=d.device)
     _check(load().psh_merge_topk(d.device.index, _stream_ptr(d.device), d.data_ptr(), ix.data_ptr(), B, n, k,
@@ -1028,9 +986,7 @@ def merge_topk_gathered(gathered: torch.Tensor, G: int, B: int, k_in: int, k: in
     g = _dev_tensor(gathered, torch.int32, "gathered")
     if tuple(g.shape) != (G, 3 * B * k_in):
         raise ValueError("gathered must be (G, 3*B*k_in) int32")
-    need = C.c_size_t(0)
-    _check(load().psh_merge_workspace_bytes(B, k, C.byref(need)), "psh_merge_workspace_bytes")
-    ws = torch.empty(int(need.value), dtype=torch.uint8, device=g.device)
+    ws = torch.empty(merge_workspace_bytes(B, k), dtype=torch.uint8, device=g.device)
     out_d = torch.empty((B, k), dtype=torch.float32, device=g.device)
     out_idx = torch.empty((B, k, 2), dtype=torch.int32, device=g.device)
     base = g.data_ptr()
@@ -1046,9 +1002,7 @@ def merge_topk_gathered(gathered: torch.Tensor, G: int, B: int, k_in: int, k: in
 
 
 def merge_workspace_bytes(B: int, k: int) -> int:
-    need = C.c_size_t(0)
-    _check(load().psh_merge_workspace_bytes(B, k, C.byref(need)), "psh_merge_workspace_bytes")
-    return int(need.value)
+    return _workspace_bytes(load().psh_merge_workspace_bytes, B, k)
 
 
 def merge_sorted_supported(G: int, k_in: int) -> bool:
@@ -1088,9 +1042,8 @@ def gather_paths(dataset: torch.Tensor, idx: torch.Tensor, length: int, r_offset
     return out
 
 
-def weighted_moments(values: torch.Tensor, weights: torch.Tensor | None):
-    """(mean, std) over axis 1 of a (B, k, ...) float32 statistic with (B, k) float64 weights (None: uniform) --
-    predict_from_paths()'s `proba.avg(values, axis=1)`, `proba.std(values, axis=1)` on the device; float64 (B, ...)."""
+def _values(values):
+    """(v, B, k, m): the (B, k, ...) float32 statistic and its m values per path."""
     v = _dev_tensor(values, torch.float32, "values")
     if v.dim() < 2:
         raise ValueError("values must be (B, k, ...)")
@@ -1098,15 +1051,29 @@ def weighted_moments(values: torch.Tensor, weights: torch.Tensor | None):
     m = v.numel() // (B * k) if B * k else 0
     if m == 0:
         raise ValueError("values is empty")
-    w_ptr = None
-    if weights is not None:
-        w = _dev_tensor(weights, torch.float64, "weights")
-        if tuple(w.shape) != (B, k):
-            raise ValueError(f"weights must be (B, k) = ({B}, {k}), got {tuple(w.shape)}")
-        w_ptr = w.data_ptr()
+    return v, B, k, m
+
+
+def _weights(weights, B: int, k: int, sets: bool = False):
+    """The (B, k) float64 weights of a statistic -- with sets=True (E, B, k) weight sets -- or None for unit weights."""
+    if weights is None:
+        return None
+    w = _dev_tensor(weights, torch.float64, "weights")
+    if sets and (w.dim() != 3 or tuple(w.shape[1:]) != (B, k)):
+        raise ValueError(f"weights must be (E, B, k) with (B, k) = ({B}, {k}), got {tuple(w.shape)}")
+    if not sets and tuple(w.shape) != (B, k):
+        raise ValueError(f"weights must be (B, k) = ({B}, {k}), got {tuple(w.shape)}")
+    return w
+
+
+def weighted_moments(values: torch.Tensor, weights: torch.Tensor | None):
+    """(mean, std) over axis 1 of a (B, k, ...) float32 statistic with (B, k) float64 weights (None: uniform) --
+    predict_from_paths()'s `proba.avg(values, axis=1)`, `proba.std(values, axis=1)` on the device; float64 (B, ...)."""
+    v, B, k, m = _values(values)
+    w = _weights(weights, B, k)
     mean = torch.empty((B,) + tuple(v.shape[2:]), dtype=torch.float64, device=v.device)
     std = torch.empty_like(mean)
-    _check(load().psh_weighted_moments(v.device.index, _stream_ptr(v.device), v.data_ptr(), w_ptr, B, k, m,
+    _check(load().psh_weighted_moments(v.device.index, _stream_ptr(v.device), v.data_ptr(), _ptr(w), B, k, m,
                                        mean.data_ptr(), std.data_ptr()), "psh_weighted_moments")
     return mean, std
 
@@ -1119,25 +1086,14 @@ def weighted_quantiles(values: torch.Tensor, weights: torch.Tensor | None, level
     """psh_weighted_quantiles over axis 1 of a (B, k, ...) float32 statistic with (B, k) float64 weights (None: unit
     weights) at the levels 0 < p < 1: (q, lower, upper), each (B, Q, ...) float64, and status (B,) int32, all on the device;
     nothing is synchronised here."""
-    v = _dev_tensor(values, torch.float32, "values")
-    if v.dim() < 2:
-        raise ValueError("values must be (B, k, ...)")
-    B, k = v.shape[:2]
-    m = v.numel() // (B * k) if B * k else 0
-    if m == 0:
-        raise ValueError("values is empty")
+    v, B, k, m = _values(values)
     lv = [float(p) for p in levels]
-    w_ptr = None
-    if weights is not None:
-        w = _dev_tensor(weights, torch.float64, "weights")
-        if tuple(w.shape) != (B, k):
-            raise ValueError(f"weights must be (B, k) = ({B}, {k}), got {tuple(w.shape)}")
-        w_ptr = w.data_ptr()
+    w = _weights(weights, B, k)
     shape = (B, len(lv)) + tuple(v.shape[2:])
     q, lower, upper = (torch.empty(shape, dtype=torch.float64, device=v.device) for _ in range(3))
     status = torch.empty((B,), dtype=torch.int32, device=v.device)
     arr = (C.c_double * max(len(lv), 1))(*lv)
-    _check(load().psh_weighted_quantiles(v.device.index, _stream_ptr(v.device), v.data_ptr(), w_ptr, B, k, m, arr, len(lv),
+    _check(load().psh_weighted_quantiles(v.device.index, _stream_ptr(v.device), v.data_ptr(), _ptr(w), B, k, m, arr, len(lv),
                                          q.data_ptr(), lower.data_ptr(), upper.data_ptr(), status.data_ptr()),
            "psh_weighted_quantiles")
     return q, lower, upper, status
@@ -1151,26 +1107,16 @@ def score_ensemble(values: torch.Tensor, weights: torch.Tensor | None, obs: torc
     """psh_score_ensemble over axis 1 of a (B, k, ...) float32 statistic against the (B, ...) float32 observations, under
     (E, B, k) float64 weight sets (None: one set of unit weights): (crps, pit_lo, pit_hi, mean), each (E, B, ...) float64,
     and status (E, B) int32, all on the device; nothing is synchronised here."""
-    v = _dev_tensor(values, torch.float32, "values")
-    if v.dim() < 2:
-        raise ValueError("values must be (B, k, ...)")
-    B, k = v.shape[:2]
-    m = v.numel() // (B * k) if B * k else 0
-    if m == 0:
-        raise ValueError("values is empty")
+    v, B, k, m = _values(values)
     y = _dev_tensor(obs, torch.float32, "obs")
     if tuple(y.shape) != (B,) + tuple(v.shape[2:]):
         raise ValueError(f"obs must be {(B,) + tuple(v.shape[2:])}, got {tuple(y.shape)}")
-    E, w_ptr = 1, None
-    if weights is not None:
-        w = _dev_tensor(weights, torch.float64, "weights")
-        if w.dim() != 3 or tuple(w.shape[1:]) != (B, k):
-            raise ValueError(f"weights must be (E, B, k) with (B, k) = ({B}, {k}), got {tuple(w.shape)}")
-        E, w_ptr = int(w.shape[0]), w.data_ptr()
+    w = _weights(weights, B, k, sets=True)
+    E = 1 if w is None else int(w.shape[0])
     shape = (E, B) + tuple(v.shape[2:])
     crps, pit_lo, pit_hi, mean = (torch.empty(shape, dtype=torch.float64, device=v.device) for _ in range(4))
     status = torch.empty((E, B), dtype=torch.int32, device=v.device)
-    _check(load().psh_score_ensemble(v.device.index, _stream_ptr(v.device), v.data_ptr(), w_ptr, y.data_ptr(), B, k, m, E,
+    _check(load().psh_score_ensemble(v.device.index, _stream_ptr(v.device), v.data_ptr(), _ptr(w), y.data_ptr(), B, k, m, E,
                                      crps.data_ptr(), pit_lo.data_ptr(), pit_hi.data_ptr(), mean.data_ptr(),
                                      status.data_ptr()), "psh_score_ensemble")
     return crps, pit_lo, pit_hi, mean, status
@@ -1193,6 +1139,26 @@ def _uniform_rows(x: torch.Tensor):
                 return None
         n *= x.shape[dim]
     return n, (rs if rs is not None else x.shape[-1])
+
+
+def _strided_rows(x, name: str):
+    """(n_rows, row_stride) of a non-empty float32 HIP tensor (..., n) whose rows lie a constant stride apart."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise NativeLibraryError(f"{name} must be a tensor on a HIP device (got {type(x).__name__} on "
+                                 f"{getattr(x, 'device', '?')}); there is no CPU path here")
+    if x.dtype != torch.float32:
+        raise TypeError(f"{name} must be torch.float32, got {x.dtype}")
+    rows = _uniform_rows(x) if x.numel() else None
+    if rows is None:
+        raise ValueError(f"{name} must be non-empty rows of samples a constant stride apart, the last dimension contiguous")
+    return rows
+
+
+def _psi_hat(psi_hat, J: int, n: int, device):
+    """The check of the scattering entry points' (J, n / 2) float64 multipliers."""
+    if not (isinstance(psi_hat, torch.Tensor) and psi_hat.device == device and psi_hat.dtype == torch.float64
+            and psi_hat.is_contiguous() and tuple(psi_hat.shape) == (J, n // 2)):
+        raise ValueError(f"psi_hat must be a contiguous ({J}, {n // 2}) float64 tensor on {device}")
 
 
 def realized_variance(x: torch.Tensor, Ts, vol: bool = False) -> torch.Tensor | None:
@@ -1220,32 +1186,20 @@ PSH_MOMENTS_STATUS_ROWS_EXCLUDED = 1
 
 
 def lagged_moments_workspace_bytes(R: int, m: int, G: int) -> int:
-    out = C.c_size_t(0)
-    _check(load().psh_lagged_moments_workspace_bytes(int(R), int(m), int(G), C.byref(out)), "psh_lagged_moments_workspace_bytes")
-    return out.value
+    return _workspace_bytes(load().psh_lagged_moments_workspace_bytes, int(R), int(m), int(G))
 
 
 def lagged_moments(x: torch.Tensor, m: int, G: int):
     """psh_lagged_moments on a float32 HIP tensor (..., n) whose rows lie a constant stride apart (contiguous, a (R, 1, n)
     ensemble, or a slice of the last dimension of one -- no copy): (sums (G, 4, m + 1) float64, rows_used (G,) int64,
     status (1,) int32), all on the device; nothing is synchronised here."""
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise NativeLibraryError(f"x must be a tensor on a HIP device (got {type(x).__name__} on "
-                                 f"{getattr(x, 'device', '?')}); there is no CPU path here")
-    if x.dtype != torch.float32:
-        raise TypeError(f"x must be torch.float32, got {x.dtype}")
-    rows = _uniform_rows(x) if x.numel() else None
-    if rows is None:
-        raise ValueError("x must be non-empty rows of samples a constant stride apart, the last dimension contiguous")
-    R, row_stride = rows
+    R, row_stride = _strided_rows(x, "x")
     n = x.shape[-1]
     sums = torch.empty((int(G), 4, int(m) + 1), dtype=torch.float64, device=x.device)
     rows_used = torch.empty((int(G),), dtype=torch.int64, device=x.device)
     status = torch.empty((1,), dtype=torch.int32, device=x.device)
     L = load()
-    nbytes = C.c_size_t(0)
-    _check(L.psh_lagged_moments_workspace_bytes(R, int(m), int(G), C.byref(nbytes)), "psh_lagged_moments_workspace_bytes")
-    ws = torch.empty((max(nbytes.value, 8) + 7) // 8, dtype=torch.int64, device=x.device)
+    ws = _workspace(L.psh_lagged_moments_workspace_bytes, R, int(m), int(G), device=x.device)
     _check(L.psh_lagged_moments(x.device.index, _stream_ptr(x.device), x.data_ptr(), R, row_stride, n, int(m), int(G),
                                 sums.data_ptr(), rows_used.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel() * 8),
            "psh_lagged_moments")
@@ -1262,10 +1216,7 @@ def scattering_nout(J: int) -> int:
 
 
 def scattering_spectra_workspace_bytes(R: int, J: int, G: int) -> int:
-    out = C.c_size_t(0)
-    _check(load().psh_scattering_spectra_workspace_bytes(int(R), int(J), int(G), C.byref(out)),
-           "psh_scattering_spectra_workspace_bytes")
-    return out.value
+    return _workspace_bytes(load().psh_scattering_spectra_workspace_bytes, int(R), int(J), int(G))
 
 
 def scattering_spectra(x: torch.Tensor, J: int, G: int, psi_hat: torch.Tensor):
@@ -1273,26 +1224,14 @@ def scattering_spectra(x: torch.Tensor, J: int, G: int, psi_hat: torch.Tensor):
     (R, 1, n) ensemble, or a slice of the last dimension of one -- no copy) with the (J, n / 2) float64 multipliers psi_hat
     on the same device: (sums (G, NOUT) float64, rows_used (G,) int64, status (1,) int32), all on the device; nothing is
     synchronised here."""
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise NativeLibraryError(f"x must be a tensor on a HIP device (got {type(x).__name__} on "
-                                 f"{getattr(x, 'device', '?')}); there is no CPU path here")
-    if x.dtype != torch.float32:
-        raise TypeError(f"x must be torch.float32, got {x.dtype}")
-    rows = _uniform_rows(x) if x.numel() else None
-    if rows is None:
-        raise ValueError("x must be non-empty rows of samples a constant stride apart, the last dimension contiguous")
-    R, row_stride = rows
+    R, row_stride = _strided_rows(x, "x")
     n, J, G = x.shape[-1], int(J), int(G)
-    if not (isinstance(psi_hat, torch.Tensor) and psi_hat.device == x.device and psi_hat.dtype == torch.float64
-            and psi_hat.is_contiguous() and tuple(psi_hat.shape) == (J, n // 2)):
-        raise ValueError(f"psi_hat must be a contiguous ({J}, {n // 2}) float64 tensor on {x.device}")
+    _psi_hat(psi_hat, J, n, x.device)
     L = load()
-    nbytes = C.c_size_t(0)
-    _check(L.psh_scattering_spectra_workspace_bytes(R, J, G, C.byref(nbytes)), "psh_scattering_spectra_workspace_bytes")
+    ws = _workspace(L.psh_scattering_spectra_workspace_bytes, R, J, G, device=x.device)
     sums = torch.empty((G, scattering_nout(J)), dtype=torch.float64, device=x.device)
     rows_used = torch.empty((G,), dtype=torch.int64, device=x.device)
     status = torch.empty((1,), dtype=torch.int32, device=x.device)
-    ws = torch.empty((max(nbytes.value, 8) + 7) // 8, dtype=torch.int64, device=x.device)
     _check(L.psh_scattering_spectra(x.device.index, _stream_ptr(x.device), x.data_ptr(), R, row_stride, n, J,
                                     psi_hat.data_ptr(), G, sums.data_ptr(), rows_used.data_ptr(), status.data_ptr(),
                                     ws.data_ptr(), ws.numel() * 8), "psh_scattering_spectra")
@@ -1304,19 +1243,9 @@ def scattering_vjp(x: torch.Tensor, J: int, G: int, psi_hat: torch.Tensor, cot: 
     float64 of the group sums: (grad (R, n) float64, status (1,) int32) on the device, grad[r] the gradient of
     sum_o cot[group of r][o] out_o(x_r) with respect to row r.  out: a float64 (R, >= n) tensor whose rows lie a constant
     stride apart, written in place on its first n columns (the rest is left untouched).  Nothing is synchronised here."""
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise NativeLibraryError(f"x must be a tensor on a HIP device (got {type(x).__name__} on "
-                                 f"{getattr(x, 'device', '?')}); there is no CPU path here")
-    if x.dtype != torch.float32:
-        raise TypeError(f"x must be torch.float32, got {x.dtype}")
-    rows = _uniform_rows(x) if x.numel() else None
-    if rows is None:
-        raise ValueError("x must be non-empty rows of samples a constant stride apart, the last dimension contiguous")
-    R, row_stride = rows
+    R, row_stride = _strided_rows(x, "x")
     n, J, G = x.shape[-1], int(J), int(G)
-    if not (isinstance(psi_hat, torch.Tensor) and psi_hat.device == x.device and psi_hat.dtype == torch.float64
-            and psi_hat.is_contiguous() and tuple(psi_hat.shape) == (J, n // 2)):
-        raise ValueError(f"psi_hat must be a contiguous ({J}, {n // 2}) float64 tensor on {x.device}")
+    _psi_hat(psi_hat, J, n, x.device)
     nout = scattering_nout(J)
     if not (isinstance(cot, torch.Tensor) and cot.device == x.device and cot.dtype == torch.float64
             and cot.is_contiguous() and tuple(cot.shape) == (G, nout)):
@@ -1329,18 +1258,16 @@ def scattering_vjp(x: torch.Tensor, J: int, G: int, psi_hat: torch.Tensor, cot: 
             raise ValueError(f"out must be a ({R}, >= {n}) float64 tensor on {x.device}, its last dimension contiguous")
         grad, grad_stride = out[:, :n], (out.stride(0) if R > 1 else max(out.shape[1], n))
     L = load()
-    nbytes = C.c_size_t(0)
-    _check(L.psh_scattering_vjp_workspace_bytes(R, n, J, G, C.byref(nbytes)), "psh_scattering_vjp_workspace_bytes")
+    ws = _workspace(L.psh_scattering_vjp_workspace_bytes, R, n, J, G, device=x.device)
     status = torch.empty((1,), dtype=torch.int32, device=x.device)
-    ws = torch.empty((max(nbytes.value, 8) + 7) // 8, dtype=torch.int64, device=x.device)
     _check(L.psh_scattering_vjp(x.device.index, _stream_ptr(x.device), x.data_ptr(), R, row_stride, n, J,
                                 psi_hat.data_ptr(), G, cot.data_ptr(), grad.data_ptr(), grad_stride, status.data_ptr(),
                                 ws.data_ptr(), ws.numel() * 8), "psh_scattering_vjp")
     return grad, status
 
 
-def _hmc_inputs(dlnx, weights, Ts, Ms):
-    """The checks hedged_mc and hedge_replay share: (x, row_stride, weights tensor or None, Ts, Ms)."""
+def _hmc_inputs(dlnx, weights, Ts, Ms, x_init, rate, degree, kind):
+    """The checks hedged_mc and hedge_replay share: (x, Ts, Ms, the arguments both entry points begin with)."""
     x = dlnx
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
         raise NativeLibraryError(f"dlnx must be a tensor on a HIP device (got {type(x).__name__}); there is no CPU path here")
@@ -1360,7 +1287,10 @@ def _hmc_inputs(dlnx, weights, Ts, Ms):
             raise ValueError(f"weights must be (B, k) = ({B}, {k}), got {tuple(w.shape)}")
         if w.device != x.device:
             raise ValueError("weights and dlnx must be on the same device")
-    return x, rows[1], w, [int(T) for T in Ts], [float(M) for M in Ms]
+    Ts, Ms = [int(T) for T in Ts], [float(M) for M in Ms]
+    nT, nM = len(Ts), len(Ms)
+    return x, Ts, Ms, (x.device.index, _stream_ptr(x.device), x.data_ptr(), rows[1], B, k, L, _ptr(w), float(x_init), float(rate),
+                       (C.c_int * max(nT, 1))(*Ts), nT, (C.c_double * max(nM, 1))(*Ms), nM, int(degree), int(kind))
 
 
 def hedged_mc(dlnx: torch.Tensor, weights: torch.Tensor | None, Ts, Ms, x_init: float = 100.0, rate: float = 0.0,
@@ -1369,25 +1299,18 @@ def hedged_mc(dlnx: torch.Tensor, weights: torch.Tensor | None, Ts, Ms, x_init: 
     or the out-context view `paths[:, :, c, W:]` of gathered paths -- no copy); weights (B, k) float64 or None (uniform).
     Returns device tensors: price / iv / strike (B, nT, nM) float64, sigma (B, nT) float64, status (B,) int32.
     policy=True: psh_hedged_mc_policy, which adds "policy" (B, nT, nM, max Ts, 2 degree + 4) float64 (include/psh.h)."""
-    x, row_stride, w, Ts, Ms = _hmc_inputs(dlnx, weights, Ts, Ms)
-    B, k, L = x.shape
-    w_ptr = None if w is None else w.data_ptr()
-    nT, nM = len(Ts), len(Ms)
+    x, Ts, Ms, head = _hmc_inputs(dlnx, weights, Ts, Ms, x_init, rate, degree, kind)
+    B, nT, nM = x.shape[0], len(Ts), len(Ms)
     out = {name: torch.empty((B, nT, nM), dtype=torch.float64, device=x.device) for name in ("price", "iv", "strike")}
     out["sigma"] = torch.empty((B, nT), dtype=torch.float64, device=x.device)
     out["status"] = torch.empty((B,), dtype=torch.int32, device=x.device)
-    args = (x.device.index, _stream_ptr(x.device), x.data_ptr(), row_stride, B, k, L, w_ptr,
-            float(x_init), float(rate), (C.c_int * max(nT, 1))(*Ts), nT,
-            (C.c_double * max(nM, 1))(*Ms), nM, int(degree), int(kind), out["price"].data_ptr(),
-            out["iv"].data_ptr(), out["strike"].data_ptr(), out["sigma"].data_ptr(),
-            out["status"].data_ptr())
+    args = head + tuple(out[name].data_ptr() for name in ("price", "iv", "strike", "sigma", "status"))
     if not policy:
         _check(load().psh_hedged_mc(*args), "psh_hedged_mc")
         return out
-    n = C.c_size_t(0)
-    _check(load().psh_hmc_policy_doubles(B, nT, nM, max(Ts, default=0), int(degree), C.byref(n)), "psh_hmc_policy_doubles")
+    n = _workspace_bytes(load().psh_hmc_policy_doubles, B, nT, nM, max(Ts, default=0), int(degree))
     out["policy"] = torch.empty((B, nT, nM, max(Ts), 2 * int(degree) + 4), dtype=torch.float64, device=x.device)
-    assert out["policy"].numel() == n.value
+    assert out["policy"].numel() == n
     _check(load().psh_hedged_mc_policy(*args, out["policy"].data_ptr()), "psh_hedged_mc_policy")
     return out
 
@@ -1398,9 +1321,8 @@ def hedge_replay(dlnx: torch.Tensor, weights: torch.Tensor | None, Ts, Ms, polic
     """psh_hedge_replay: the policy (B, nT, nM, max Ts, 2 degree + 4) of a fit, with the fit's strike and price
     (B, nT, nM) and its x_init, rate, Ts, Ms, degree, kind, replayed on float32 log-returns (B, k', L) (as hedged_mc's; any
     k').  Returns device tensors: sums (B, nT, nM, 9) float64, status (B,) int32, and pnl (B, nT, nM, k') when asked for."""
-    x, row_stride, w, Ts, Ms = _hmc_inputs(dlnx, weights, Ts, Ms)
-    B, k, L = x.shape
-    nT, nM = len(Ts), len(Ms)
+    x, Ts, Ms, head = _hmc_inputs(dlnx, weights, Ts, Ms, x_init, rate, degree, kind)
+    (B, k), nT, nM = x.shape[:2], len(Ts), len(Ms)
     pol = _dev_tensor(policy, torch.float64, "policy").contiguous()
     if tuple(pol.shape) != (B, nT, nM, max(Ts, default=0), 2 * int(degree) + 4):
         raise ValueError(f"policy must be (B, nT, nM, max Ts, 2 degree + 4), got {tuple(pol.shape)}")
@@ -1414,15 +1336,9 @@ def hedge_replay(dlnx: torch.Tensor, weights: torch.Tensor | None, Ts, Ms, polic
            "status": torch.empty((B,), dtype=torch.int32, device=x.device)}
     if return_pnl:
         out["pnl"] = torch.empty((B, nT, nM, k), dtype=torch.float64, device=x.device)
-    nbytes = C.c_size_t(0)
-    _check(load().psh_hedge_replay_workspace_bytes(B, k, nT, nM, C.byref(nbytes)), "psh_hedge_replay_workspace_bytes")
-    ws = torch.empty((max(nbytes.value, 8) + 7) // 8, dtype=torch.int64, device=x.device)
-    _check(load().psh_hedge_replay(x.device.index, _stream_ptr(x.device), x.data_ptr(), row_stride, B, k, L,
-                                   None if w is None else w.data_ptr(), float(x_init), float(rate),
-                                   (C.c_int * max(nT, 1))(*Ts), nT, (C.c_double * max(nM, 1))(*Ms), nM, int(degree),
-                                   int(kind), pol.data_ptr(), ks.data_ptr(), ce.data_ptr(), out["sums"].data_ptr(),
-                                   out["pnl"].data_ptr() if return_pnl else None, out["status"].data_ptr(),
-                                   ws.data_ptr(), ws.numel() * 8), "psh_hedge_replay")
+    ws = _workspace(load().psh_hedge_replay_workspace_bytes, B, k, nT, nM, device=x.device)
+    _check(load().psh_hedge_replay(*head, pol.data_ptr(), ks.data_ptr(), ce.data_ptr(), out["sums"].data_ptr(), _ptr(out.get("pnl")),
+                                   out["status"].data_ptr(), ws.data_ptr(), ws.numel() * 8), "psh_hedge_replay")
     return out
 
 
@@ -1485,27 +1401,24 @@ def _dlnx_rows(R: int, n: int, dev, dlnx_out):
     return dlnx_out, (dlnx_out.stride(0) if R > 1 else n)
 
 
-def mrw_generate(R: int, n: int, sigma: float, a_omega: torch.Tensor, a_eps: torch.Tensor | None, c0: float, *,
-                 seed: int = 0, outputs=("dlnx",), dlnx_out: torch.Tensor | None = None) -> dict:
-    """psh_mrw_generate: R multifractal random walks of n returns (shadowing_amd/mrw.py computes the tables).  a_omega,
-    a_eps: (M,) float64 device tensors, M the smallest power of two >= 2n (a_eps None: H = 0.5).  Returns a dict of the
-    requested `outputs` (of MRW_OUTPUTS) as device tensors: "dlnx" (R, 1, n) float32, "lnx" (R, n + 1) and "omega" (R, n)
-    float64.  dlnx_out: a float32 device tensor (R, ..) whose rows (stride(0) >= n floats apart, unit stride inside) take
-    the returns instead of a fresh tensor; whatever lies between the rows is left alone.  Nothing is synchronised."""
-    bad = [o for o in outputs if o not in MRW_OUTPUTS]
+def _mrw_generate(entry: str, names, R: int, n: int, tables, m, outputs, dlnx_out):
+    """What mrw_generate and smrw_generate share: the output names, M, the tables' checks, the output tensors.  tables:
+    (name, tensor, dtype) each, on the first one's device; m: the leverage kernel's lags, or None.  (device, out, row stride)."""
+    bad = [o for o in outputs if o not in names]
     if bad:
-        raise ValueError(f"unknown outputs {bad}; choose from {MRW_OUTPUTS}")
+        raise ValueError(f"unknown outputs {bad}; choose from {names}")
     if n > PSH_MRW_MAX_N:
-        raise ValueError(f"psh_mrw_generate makes paths of n <= {PSH_MRW_MAX_N} returns, got {n}")
+        raise ValueError(f"{entry} makes paths of n <= {PSH_MRW_MAX_N} returns, got {n}")
     M = 4
     while M < 2 * n:
         M *= 2
-    a_omega = _dev_tensor(a_omega, torch.float64, "a_omega")
-    dev = a_omega.device
-    if a_eps is not None:
-        a_eps = _dev_tensor(a_eps, torch.float64, "a_eps")
-    for name, t in (("a_omega", a_omega), ("a_eps", a_eps)):
-        if t is not None and (tuple(t.shape) != (M,) or t.device != dev):
+    if m is not None and not 1 <= m <= M - n:
+        raise ValueError(f"the memory must satisfy 1 <= m <= M - n = {M - n}, got {m}")
+    for name, t, dtype in tables:
+        _dev_tensor(t, dtype, name)
+    dev = tables[0][1].device
+    for name, t, _ in tables:
+        if tuple(t.shape) != (M,) or t.device != dev:
             raise ValueError(f"{name} must hold M = {M} values on {dev}, got {tuple(t.shape)} on {t.device}")
     out = {}
     stride = n
@@ -1513,12 +1426,23 @@ def mrw_generate(R: int, n: int, sigma: float, a_omega: torch.Tensor, a_eps: tor
         out["dlnx"], stride = _dlnx_rows(R, n, dev, dlnx_out)
     if "lnx" in outputs:
         out["lnx"] = torch.empty((R, n + 1), dtype=torch.float64, device=dev)
-    if "omega" in outputs:
-        out["omega"] = torch.empty((R, n), dtype=torch.float64, device=dev)
-    ptr = lambda name: out[name].data_ptr() if name in out else None   # noqa: E731
-    _check(load().psh_mrw_generate(dev.index, _stream_ptr(dev), int(R), int(n), float(sigma), a_omega.data_ptr(),
-                                   None if a_eps is None else a_eps.data_ptr(), float(c0), int(seed), ptr("dlnx"),
-                                   int(stride), ptr("lnx"), ptr("omega")), "psh_mrw_generate")
+    if names[2] in outputs:
+        out[names[2]] = torch.empty((R, n), dtype=torch.float64, device=dev)
+    return dev, out, int(stride)
+
+
+def mrw_generate(R: int, n: int, sigma: float, a_omega: torch.Tensor, a_eps: torch.Tensor | None, c0: float, *,
+                 seed: int = 0, outputs=("dlnx",), dlnx_out: torch.Tensor | None = None) -> dict:
+    """psh_mrw_generate: R multifractal random walks of n returns (shadowing_amd/mrw.py computes the tables).  a_omega,
+    a_eps: (M,) float64 device tensors, M the smallest power of two >= 2n (a_eps None: H = 0.5).  Returns a dict of the
+    requested `outputs` (of MRW_OUTPUTS) as device tensors: "dlnx" (R, 1, n) float32, "lnx" (R, n + 1) and "omega" (R, n)
+    float64.  dlnx_out: a float32 device tensor (R, ..) whose rows (stride(0) >= n floats apart, unit stride inside) take
+    the returns instead of a fresh tensor; whatever lies between the rows is left alone.  Nothing is synchronised."""
+    tables = [("a_omega", a_omega, torch.float64)] + ([] if a_eps is None else [("a_eps", a_eps, torch.float64)])
+    dev, out, stride = _mrw_generate("psh_mrw_generate", MRW_OUTPUTS, R, n, tables, None, outputs, dlnx_out)
+    _check(load().psh_mrw_generate(dev.index, _stream_ptr(dev), int(R), int(n), float(sigma), a_omega.data_ptr(), _ptr(a_eps),
+                                   float(c0), int(seed), _ptr(out.get("dlnx")), stride, _ptr(out.get("lnx")),
+                                   _ptr(out.get("omega"))), "psh_mrw_generate")
     return out
 
 
@@ -1532,34 +1456,11 @@ def smrw_generate(R: int, n: int, m: int, sigma: float, a_omega: torch.Tensor, k
     smallest power of two >= 2n, 1 <= m <= M - n.  Returns a dict of the requested `outputs` (of SMRW_OUTPUTS) as device
     tensors: "dlnx" (R, 1, n) float32, "lnx" (R, n + 1) and "logvol" (R, n) float64.  dlnx_out: as mrw_generate.  Nothing
     is synchronised."""
-    bad = [o for o in outputs if o not in SMRW_OUTPUTS]
-    if bad:
-        raise ValueError(f"unknown outputs {bad}; choose from {SMRW_OUTPUTS}")
-    if n > PSH_MRW_MAX_N:
-        raise ValueError(f"psh_smrw_generate makes paths of n <= {PSH_MRW_MAX_N} returns, got {n}")
-    M = 4
-    while M < 2 * n:
-        M *= 2
-    if not 1 <= m <= M - n:
-        raise ValueError(f"the memory must satisfy 1 <= m <= M - n = {M - n}, got {m}")
-    a_omega = _dev_tensor(a_omega, torch.float64, "a_omega")
-    dev = a_omega.device
-    k_hat = _dev_tensor(k_hat, torch.complex128, "k_hat")
-    for name, t in (("a_omega", a_omega), ("k_hat", k_hat)):
-        if tuple(t.shape) != (M,) or t.device != dev:
-            raise ValueError(f"{name} must hold M = {M} values on {dev}, got {tuple(t.shape)} on {t.device}")
-    out = {}
-    stride = n
-    if "dlnx" in outputs:
-        out["dlnx"], stride = _dlnx_rows(R, n, dev, dlnx_out)
-    if "lnx" in outputs:
-        out["lnx"] = torch.empty((R, n + 1), dtype=torch.float64, device=dev)
-    if "logvol" in outputs:
-        out["logvol"] = torch.empty((R, n), dtype=torch.float64, device=dev)
-    ptr = lambda name: out[name].data_ptr() if name in out else None   # noqa: E731
+    tables = [("a_omega", a_omega, torch.float64), ("k_hat", k_hat, torch.complex128)]
+    dev, out, stride = _mrw_generate("psh_smrw_generate", SMRW_OUTPUTS, R, n, tables, m, outputs, dlnx_out)
     _check(load().psh_smrw_generate(dev.index, _stream_ptr(dev), int(R), int(n), int(m), float(sigma), a_omega.data_ptr(),
-                                    k_hat.data_ptr(), float(c0), float(v), int(seed), ptr("dlnx"), int(stride), ptr("lnx"),
-                                    ptr("logvol")), "psh_smrw_generate")
+                                    k_hat.data_ptr(), float(c0), float(v), int(seed), _ptr(out.get("dlnx")), stride,
+                                    _ptr(out.get("lnx")), _ptr(out.get("logvol"))), "psh_smrw_generate")
     return out
 
 

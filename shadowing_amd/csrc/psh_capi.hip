@@ -1,3 +1,4 @@
+#include <algorithm>
 #include <cmath>
 // psh_capi.hip -- the C ABI declared in include/psh.h: argument checking, workspace
 // carving, launch planning.  Everything is enqueued on the caller's stream; no
@@ -1526,27 +1527,43 @@ int psh_score_ensemble(int device, void* stream, const float* values, const doub
     return PSH_OK;
 }
 
+// what every hedged Monte Carlo entry point asks of the paths, the grid of maturities and strikes and the regression
+static int hmc_check_sizes(const float* dlnx, int64_t row_stride, int B, int k, int len, double x_init, double rate, const int* Ts,
+                           int nT, const double* Ms, int nM, int degree, int kind) {
+    if (!dlnx || !Ts || !Ms || B <= 0 || k <= 0 || len <= 0 || row_stride < len || nT <= 0 || nM <= 0 || degree < 1 ||
+        kind < PSH_HMC_OTM || kind > PSH_HMC_PUT || !std::isfinite(x_init) || !(x_init > 0.0) || !std::isfinite(rate))
+        return PSH_ERR_ARG;
+    if (degree > 5 || nT > PSH_HMC_MAX_T || nM > PSH_HMC_MAX_M) return PSH_ERR_UNSUPPORTED;
+    return PSH_OK;
+}
+
+// ... and the checked copy of that grid into the launch arguments (HmcArgs, HedgeReplayArgs)
+static int hmc_copy_grid(int* to_Ts, double* to_Ms, int len, const int* Ts, int nT, const double* Ms, int nM) {
+    for (int i = 0; i < nT; ++i) {
+        if (Ts[i] < 1 || Ts[i] > len) return PSH_ERR_ARG;
+        to_Ts[i] = Ts[i];
+    }
+    for (int i = 0; i < nM; ++i) {
+        if (!std::isfinite(Ms[i])) return PSH_ERR_ARG;
+        to_Ms[i] = Ms[i];
+    }
+    return PSH_OK;
+}
+
 // the argument checks and the launch arguments that psh_hedged_mc and psh_hedged_mc_policy share
 static int hmc_fill_args(HmcArgs& a, const float* dlnx, int64_t row_stride, int B, int k, int len, const double* weights,
                          double x_init, double rate, const int* Ts, int nT, const double* Ms, int nM, int degree, int kind,
                          double* out_price, double* out_iv, double* out_strike, double* out_sigma, int32_t* out_status) {
-    if (!dlnx || !Ts || !Ms || !out_price || !out_iv || !out_strike || B <= 0 || k <= 0 || len <= 0 || row_stride < len ||
-        nT <= 0 || nM <= 0 || degree < 1 || kind < PSH_HMC_OTM || kind > PSH_HMC_PUT || !std::isfinite(x_init) ||
-        !(x_init > 0.0) || !std::isfinite(rate))
-        return PSH_ERR_ARG;
-    if (k > PSH_MAX_K || degree > 5 || nT > PSH_HMC_MAX_T || nM > PSH_HMC_MAX_M) return PSH_ERR_UNSUPPORTED;
+    if (!out_price || !out_iv || !out_strike) return PSH_ERR_ARG;
+    int rc = hmc_check_sizes(dlnx, row_stride, B, k, len, x_init, rate, Ts, nT, Ms, nM, degree, kind);
+    if (rc != PSH_OK) return rc;
+    if (k > PSH_MAX_K) return PSH_ERR_UNSUPPORTED;
     if ((int64_t)B * k * row_stride >= ((int64_t)1 << 40) || (int64_t)B * nT * ((nM + PSH_HMC_SG - 1) / PSH_HMC_SG) >= ((int64_t)1 << 31))
         return PSH_ERR_UNSUPPORTED;
     a.x = dlnx; a.row_stride = row_stride; a.B = B; a.k = k; a.len = len; a.w = weights; a.x_init = x_init; a.rate = rate;
     a.nT = nT; a.nM = nM; a.degree = degree; a.kind = kind; a.ngroups = (nM + PSH_HMC_SG - 1) / PSH_HMC_SG;
-    for (int i = 0; i < nT; ++i) {
-        if (Ts[i] < 1 || Ts[i] > len) return PSH_ERR_ARG;
-        a.Ts[i] = Ts[i];
-    }
-    for (int i = 0; i < nM; ++i) {
-        if (!std::isfinite(Ms[i])) return PSH_ERR_ARG;
-        a.Ms[i] = Ms[i];
-    }
+    rc = hmc_copy_grid(a.Ts, a.Ms, len, Ts, nT, Ms, nM);
+    if (rc != PSH_OK) return rc;
     a.price = out_price; a.iv = out_iv; a.strike = out_strike; a.sigma = out_sigma; a.status = out_status;
     return PSH_OK;
 }
@@ -1597,25 +1614,17 @@ int psh_hedge_replay(int device, void* stream, const float* dlnx, int64_t row_st
                      const double* weights, double x_init, double rate, const int* Ts, int nT, const double* Ms, int nM,
                      int degree, int kind, const double* policy, const double* strike, const double* centre,
                      double* out_sums, double* out_pnl, int32_t* out_status, void* workspace, size_t workspace_bytes) {
-    if (!dlnx || !Ts || !Ms || !policy || !strike || !centre || !out_sums || !workspace || B <= 0 || k <= 0 || len <= 0 ||
-        row_stride < len || nT <= 0 || nM <= 0 || degree < 1 || kind < PSH_HMC_OTM || kind > PSH_HMC_PUT ||
-        !std::isfinite(x_init) || !(x_init > 0.0) || !std::isfinite(rate))
-        return PSH_ERR_ARG;
-    if (degree > 5 || nT > PSH_HMC_MAX_T || nM > PSH_HMC_MAX_M) return PSH_ERR_UNSUPPORTED;
+    if (!policy || !strike || !centre || !out_sums || !workspace) return PSH_ERR_ARG;
+    int rc = hmc_check_sizes(dlnx, row_stride, B, k, len, x_init, rate, Ts, nT, Ms, nM, degree, kind);
+    if (rc != PSH_OK) return rc;
     HedgeReplayArgs a{};
     a.ngroups = (nM + PSH_HMC_SG - 1) / PSH_HMC_SG;
     a.ntiles = (int)(((int64_t)k + PSH_HEDGE_TILE - 1) / PSH_HEDGE_TILE);
     if ((int64_t)B * k * row_stride >= ((int64_t)1 << 40) || (int64_t)B * nT * a.ngroups * a.ntiles >= ((int64_t)1 << 31))
         return PSH_ERR_UNSUPPORTED;
-    for (int i = 0; i < nT; ++i) {
-        if (Ts[i] < 1 || Ts[i] > len) return PSH_ERR_ARG;
-        a.Ts[i] = Ts[i];
-        a.Tmax = Ts[i] > a.Tmax ? Ts[i] : a.Tmax;
-    }
-    for (int i = 0; i < nM; ++i) {
-        if (!std::isfinite(Ms[i])) return PSH_ERR_ARG;
-        a.Ms[i] = Ms[i];
-    }
+    rc = hmc_copy_grid(a.Ts, a.Ms, len, Ts, nT, Ms, nM);
+    if (rc != PSH_OK) return rc;
+    a.Tmax = *std::max_element(a.Ts, a.Ts + nT);
     if (hedge_replay_lds_bytes(a.Tmax, degree) > PSH_HEDGE_MAX_LDS) return PSH_ERR_UNSUPPORTED;   // (the policy rows sit in LDS)
     size_t need = 0;
     psh_hedge_replay_workspace_bytes(B, k, nT, nM, &need);
@@ -1655,17 +1664,25 @@ int psh_pdv_generate(int device, void* stream, int B, int64_t S, int n_steps, co
     return PSH_OK;
 }
 
-int psh_mrw_generate(int device, void* stream, int64_t R, int n, double sigma, const double* a_omega, const double* a_eps,
-                     double c0, uint64_t seed, float* out_dlnx, int64_t dlnx_row_stride, double* out_lnx,
-                     double* out_omega) {
-    if (!a_omega || R < 1 || n < 2 || !std::isfinite(sigma) || sigma < 0.0 || !std::isfinite(c0) ||
-        (out_dlnx && dlnx_row_stride < n))
+// what both generators ask of the ensemble's size, the noise and the increments' row stride; log2 of the FFT length
+static int mrw_check_sizes(int64_t R, int n, double sigma, double c0, const float* out_dlnx, int64_t dlnx_row_stride, int* logM) {
+    if (R < 1 || n < 2 || !std::isfinite(sigma) || sigma < 0.0 || !std::isfinite(c0) || (out_dlnx && dlnx_row_stride < n))
         return PSH_ERR_ARG;
     if (n > PSH_MRW_MAX_N || R >= ((int64_t)1 << 32)) return PSH_ERR_UNSUPPORTED;   // (the grid is R / 2 workgroups)
     if (out_dlnx && R > INT64_MAX / dlnx_row_stride) return PSH_ERR_ARG;
+    *logM = 2;
+    while ((1 << *logM) < 2 * n) ++*logM;
+    return PSH_OK;
+}
+
+int psh_mrw_generate(int device, void* stream, int64_t R, int n, double sigma, const double* a_omega, const double* a_eps,
+                     double c0, uint64_t seed, float* out_dlnx, int64_t dlnx_row_stride, double* out_lnx,
+                     double* out_omega) {
+    if (!a_omega) return PSH_ERR_ARG;
     MrwArgs a{};
-    a.R = R; a.n = n; a.logM = 2;
-    while ((1 << a.logM) < 2 * n) ++a.logM;
+    const int rc = mrw_check_sizes(R, n, sigma, c0, out_dlnx, dlnx_row_stride, &a.logM);
+    if (rc != PSH_OK) return rc;
+    a.R = R; a.n = n;
     a.sigma = sigma; a.c0 = c0; a.key0 = (uint32_t)seed; a.key1 = (uint32_t)(seed >> 32);
     a.a_omega = a_omega; a.a_eps = a_eps;
     a.dlnx = out_dlnx; a.dlnx_stride = dlnx_row_stride; a.lnx = out_lnx; a.omega = out_omega;
@@ -1677,14 +1694,11 @@ int psh_mrw_generate(int device, void* stream, int64_t R, int n, double sigma, c
 int psh_smrw_generate(int device, void* stream, int64_t R, int n, int m, double sigma, const double* a_omega,
                       const double* k_hat, double c0, double v, uint64_t seed, float* out_dlnx, int64_t dlnx_row_stride,
                       double* out_lnx, double* out_logvol) {
-    if (!a_omega || !k_hat || R < 1 || n < 2 || m < 1 || !std::isfinite(sigma) || sigma < 0.0 || !std::isfinite(c0) ||
-        !std::isfinite(v) || (out_dlnx && dlnx_row_stride < n))
-        return PSH_ERR_ARG;
-    if (n > PSH_MRW_MAX_N || R >= ((int64_t)1 << 32)) return PSH_ERR_UNSUPPORTED;   // (the grid is R / 2 workgroups)
-    if (out_dlnx && R > INT64_MAX / dlnx_row_stride) return PSH_ERR_ARG;
+    if (!a_omega || !k_hat || m < 1 || !std::isfinite(v)) return PSH_ERR_ARG;
     SmrwArgs a{};
-    a.R = R; a.n = n; a.m = m; a.logM = 2;
-    while ((1 << a.logM) < 2 * n) ++a.logM;
+    const int rc = mrw_check_sizes(R, n, sigma, c0, out_dlnx, dlnx_row_stride, &a.logM);
+    if (rc != PSH_OK) return rc;
+    a.R = R; a.n = n; a.m = m;
     if (m > (1 << a.logM) - n) return PSH_ERR_ARG;           // the convolution would wrap
     a.sigma = sigma; a.cv = c0 + v; a.key0 = (uint32_t)seed; a.key1 = (uint32_t)(seed >> 32);
     a.a_omega = a_omega; a.k_hat = (const double2*)k_hat;
@@ -1730,6 +1744,17 @@ int psh_lagged_moments(int device, void* stream, const float* x, int64_t R, int6
     return PSH_OK;
 }
 
+// what the scattering spectra and their gradient ask of the row length n, the scales J and the groups G; log2(n)
+static int scattering_check_sizes(int64_t R, int n, int J, int64_t G, int* logn_out) {
+    if (n < 8 || (n & (n - 1)) != 0 || R < 1 || J < 1 || G < 1 || G > R) return PSH_ERR_ARG;
+    int logn = 3;
+    while (logn < 30 && (1 << logn) < n) ++logn;
+    if (J > logn - 2) return PSH_ERR_ARG;
+    if (n > PSH_SCAT_MAX_N) return PSH_ERR_UNSUPPORTED;
+    *logn_out = logn;
+    return PSH_OK;
+}
+
 // the argument checks both psh_scattering_spectra entry points share, and the plan (units, outputs) for the sizes
 static int scattering_spectra_plan(int64_t R, int J, int64_t G, ScatArgs* a, size_t* bytes) {
     if (R < 1 || J < 1 || G < 1 || G > R) return PSH_ERR_ARG;
@@ -1750,16 +1775,13 @@ int psh_scattering_spectra_workspace_bytes(int64_t R, int J, int64_t G, size_t* 
 int psh_scattering_spectra(int device, void* stream, const float* x, int64_t R, int64_t row_stride, int n, int J,
                            const double* psi_hat, int64_t G, double* out_sums, int64_t* out_rows_used,
                            int32_t* out_status, void* workspace, size_t workspace_bytes) {
-    if (!x || !psi_hat || !out_sums || !out_rows_used || !workspace || n < 8 || (n & (n - 1)) != 0 || row_stride < n ||
-        R < 1 || J < 1 || G < 1 || G > R)
-        return PSH_ERR_ARG;
-    int logn = 3;
-    while (logn < 30 && (1 << logn) < n) ++logn;
-    if (J > logn - 2) return PSH_ERR_ARG;
-    if (n > PSH_SCAT_MAX_N) return PSH_ERR_UNSUPPORTED;
+    if (!x || !psi_hat || !out_sums || !out_rows_used || !workspace || row_stride < n) return PSH_ERR_ARG;
+    int logn = 0;
+    int rc = scattering_check_sizes(R, n, J, G, &logn);
+    if (rc != PSH_OK) return rc;
     ScatArgs a{};
     size_t need = 0;
-    const int rc = scattering_spectra_plan(R, J, G, &a, &need);
+    rc = scattering_spectra_plan(R, J, G, &a, &need);
     if (rc != PSH_OK) return rc;
     if (R > INT64_MAX / row_stride) return PSH_ERR_ARG;
     if (workspace_bytes < need) return PSH_ERR_WORKSPACE;
@@ -1774,12 +1796,9 @@ int psh_scattering_spectra(int device, void* stream, const float* x, int64_t R, 
 
 // the argument checks both psh_scattering_vjp entry points share (the forward's), log2(n) and the workspace for the sizes
 static int scattering_vjp_plan(int64_t R, int n, int J, int64_t G, int* logn_out, size_t* bytes) {
-    if (n < 8 || (n & (n - 1)) != 0 || R < 1 || J < 1 || G < 1 || G > R) return PSH_ERR_ARG;
-    int logn = 3;
-    while (logn < 30 && (1 << logn) < n) ++logn;
-    if (J > logn - 2) return PSH_ERR_ARG;
-    if (n > PSH_SCAT_MAX_N || R >= ((int64_t)1 << 31)) return PSH_ERR_UNSUPPORTED;          // ((r + 1) * G stays in int64)
-    *logn_out = logn;
+    const int rc = scattering_check_sizes(R, n, J, G, logn_out);
+    if (rc != PSH_OK) return rc;
+    if (R >= ((int64_t)1 << 31)) return PSH_ERR_UNSUPPORTED;                                // ((r + 1) * G stays in int64)
     *bytes = (size_t)scattering_grad_workgroups(R) * sizeof(int32_t);
     return PSH_OK;
 }

@@ -1,6 +1,7 @@
 // psh_embed.hip -- the scans behind a linear embedding (embed_scan_kernel: dense fma chains, and the suffix-rows
 // rejection test for Foveal-like kernels) and over one-window rows (rows_kernel: PathDistance.forward_topk), with their
 // launchers.  Part of libpsh_hip.so; shared device code in psh_device.h / psh_segment.h, design overview at the top of psh_scan.hip.
+#include "psh_launch.h"
 #include "psh_segment.h"
 
 namespace psh {
@@ -828,34 +829,6 @@ size_t scan_shmem_bytes(int tile_floats, int B, int emb_d, int W, int threads) {
 #define PSH_EMB_WIDE_BG 10
 #define PSH_EMB_WIDE_NBG 6
 
-template <bool ALIGNED, int MODE>
-static hipError_t launch_embed_mode(const ScanArgs& a, int grid, size_t shmem, hipStream_t s) {
-    if (a.emb_wide) {
-        hipError_t e = hipFuncSetAttribute((const void*)embed_scan_kernel<ALIGNED, MODE, PSH_EMB_WIDE_THREADS, PSH_EMB_WIDE_BG, PSH_EMB_WIDE_NBG>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((embed_scan_kernel<ALIGNED, MODE, PSH_EMB_WIDE_THREADS, PSH_EMB_WIDE_BG, PSH_EMB_WIDE_NBG>), dim3(grid),
-                           dim3(PSH_EMB_WIDE_THREADS), shmem, s, a);
-        return hipGetLastError();
-    }
-    if (shmem > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)embed_scan_kernel<ALIGNED, MODE, PSH_SCAN_THREADS, PSH_EMB_BG, PSH_NEST_BG>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((embed_scan_kernel<ALIGNED, MODE, PSH_SCAN_THREADS, PSH_EMB_BG, PSH_NEST_BG>), dim3(grid), dim3(PSH_SCAN_THREADS), shmem, s, a);
-    return hipGetLastError();
-}
-
-template <bool ALIGNED>
-static hipError_t launch_embed(const ScanArgs& a, int mode, int grid, size_t shmem, hipStream_t s) {
-    switch (mode) {
-        case PSH_MODE_BOOT: return launch_embed_mode<ALIGNED, PSH_MODE_BOOT>(a, grid, shmem, s);
-        case PSH_MODE_FILTER: return launch_embed_mode<ALIGNED, PSH_MODE_FILTER>(a, grid, shmem, s);
-        default: return launch_embed_mode<ALIGNED, PSH_MODE_ALL>(a, grid, shmem, s);
-    }
-}
-
 hipError_t launch_embed_scan(const ScanArgs& a, int mode, bool aligned, int grid, hipStream_t s) {
     if (a.emb_mx && (mode == PSH_MODE_FILTER || (mode == PSH_MODE_BOOT && a.boot_per_wave == 2)))
         return launch_embed_mx(a, mode, aligned, grid, s);                   // psh_embed_mx.hip: dense kernel, matrix cores
@@ -864,16 +837,18 @@ hipError_t launch_embed_scan(const ScanArgs& a, int mode, bool aligned, int grid
         if (e != hipSuccess) return e;
     }
     const size_t shmem = scan_shmem_bytes(a.tile_floats, a.B, a.emb_d, a.W, a.emb_wide ? PSH_EMB_WIDE_THREADS : PSH_SCAN_THREADS);
-    return aligned ? launch_embed<true>(a, mode, grid, shmem, s) : launch_embed<false>(a, mode, grid, shmem, s);
+    return pick<PSH_MODE_BOOT, PSH_MODE_FILTER, PSH_MODE_ALL>(mode == PSH_MODE_BOOT || mode == PSH_MODE_FILTER ? mode : PSH_MODE_ALL, [&](auto MODE) {
+        return pick<true, false>(aligned, [&](auto AL) {
+            return pick<true, false>(a.emb_wide != 0, [&](auto WIDE) {
+                constexpr int THREADS = WIDE() ? PSH_EMB_WIDE_THREADS : PSH_SCAN_THREADS, BG = WIDE() ? PSH_EMB_WIDE_BG : PSH_EMB_BG,
+                              NBG = WIDE() ? PSH_EMB_WIDE_NBG : PSH_NEST_BG;
+                return launch(embed_scan_kernel<AL(), MODE(), THREADS, BG, NBG>, grid, THREADS, shmem, s, a); }); }); });
 }
 
 hipError_t embed_blocks_per_cu(bool aligned, size_t shmem, int* out) {
-    int n = 0;
-    const hipError_t e =
-        aligned ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, embed_scan_kernel<true, PSH_MODE_FILTER, PSH_SCAN_THREADS, PSH_EMB_BG, PSH_NEST_BG>, PSH_SCAN_THREADS, shmem)
-                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, embed_scan_kernel<false, PSH_MODE_FILTER, PSH_SCAN_THREADS, PSH_EMB_BG, PSH_NEST_BG>, PSH_SCAN_THREADS, shmem);
-    *out = n;
-    return e;
+    *out = 0;
+    return pick<true, false>(aligned, [&](auto AL) {
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(out, embed_scan_kernel<AL(), PSH_MODE_FILTER, PSH_SCAN_THREADS, PSH_EMB_BG, PSH_NEST_BG>, PSH_SCAN_THREADS, shmem); });
 }
 
 // ----------------------------------------------------------------------------------
@@ -900,16 +875,10 @@ __global__ __launch_bounds__(256) void embed_rows_kernel(const float* __restrict
 }
 
 hipError_t launch_embed_rows(const float* dataset, int64_t R, int64_t T, const float* ker, int d, int K, float* out, hipStream_t s) {
-    const size_t shmem = (size_t)d * K * sizeof(float);
-    if (shmem > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)embed_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (e != hipSuccess) return e;
-    }
     int64_t grid = (R * d + 255) / 256;
     if (grid > 8192) grid = 8192;
     if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(embed_rows_kernel, dim3((unsigned)grid), dim3(256), shmem, s, dataset, R, T, ker, d, K, out);
-    return hipGetLastError();
+    return launch(embed_rows_kernel, (unsigned)grid, 256, (size_t)d * K * sizeof(float), s, dataset, R, T, ker, d, K, out);
 }
 
 size_t rows_shmem_bytes(int ds, int B) {      // ds: LDS floats per row
@@ -929,20 +898,8 @@ hipError_t launch_rows(ScanArgs a, int mode, int grid, hipStream_t s) {
     }
     a.tile_floats = ds;
     const size_t shmem = rows_shmem_bytes(ds, a.B);
-    if (mode == PSH_MODE_BOOT) {
-        hipError_t e = hipFuncSetAttribute((const void*)rows_kernel<PSH_MODE_BOOT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((rows_kernel<PSH_MODE_BOOT>), dim3(grid), dim3(PSH_ROWS_THREADS), shmem, s, a, aligned16, staging);
-    } else if (mode == PSH_MODE_ALL) {
-        hipError_t e = hipFuncSetAttribute((const void*)rows_kernel<PSH_MODE_ALL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((rows_kernel<PSH_MODE_ALL>), dim3(grid), dim3(PSH_ROWS_THREADS), shmem, s, a, aligned16, staging);
-    } else {
-        hipError_t e = hipFuncSetAttribute((const void*)rows_kernel<PSH_MODE_FILTER>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((rows_kernel<PSH_MODE_FILTER>), dim3(grid), dim3(PSH_ROWS_THREADS), shmem, s, a, aligned16, staging);
-    }
-    return hipGetLastError();
+    return pick<PSH_MODE_BOOT, PSH_MODE_ALL, PSH_MODE_FILTER>(mode == PSH_MODE_BOOT || mode == PSH_MODE_ALL ? mode : PSH_MODE_FILTER, [&](auto MODE) {
+        return launch(rows_kernel<MODE()>, grid, PSH_ROWS_THREADS, shmem, s, a, aligned16, staging); });
 }
 
 

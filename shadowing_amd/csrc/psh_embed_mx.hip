@@ -43,6 +43,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "psh_launch.h"
 #include "psh_segment.h"
 
 namespace psh {
@@ -969,22 +970,6 @@ bool embed_mx_supported(int d, int K, int B, int tile_floats) {
     return d >= 1 && d <= PSH_EMX_MAX_D && K >= 1 && K <= 256 && emx_shmem_bytes(K, d, B, tile_floats) <= PSH_LDS_BYTES;
 }
 
-template <bool ALIGNED, int MODE, int NG, int NP, bool QM>
-static hipError_t launch_emx_ng(const ScanArgs& a, int grid, hipStream_t s) {
-    const size_t shmem = emx_shmem_bytes(a.W, a.emb_d, a.B, a.tile_floats);
-    hipError_t e = hipFuncSetAttribute((const void*)embed_mx_kernel<ALIGNED, MODE, NG, NP, QM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((embed_mx_kernel<ALIGNED, MODE, NG, NP, QM>), dim3(grid), dim3(PSH_EMX_THREADS), shmem, s, a);
-    return hipGetLastError();
-}
-
-template <bool ALIGNED, int MODE, int NP, bool QM>
-static hipError_t launch_emx(const ScanArgs& a, int grid, hipStream_t s) {
-    const int ng = (a.emb_d + 3) >> 2;
-    return ng == 1 ? launch_emx_ng<ALIGNED, MODE, 1, NP, QM>(a, grid, s) : ng == 2 ? launch_emx_ng<ALIGNED, MODE, 2, NP, QM>(a, grid, s)
-                                                                                  : launch_emx_ng<ALIGNED, MODE, 3, NP, QM>(a, grid, s);
-}
-
 // the bootstrap with the split products; the full scan with one product and -- 3 .. 256 queries -- the per-query pass on the
 // matrix cores too, or (a.emb_mx == 3: PSH_FLAG_EMBED_MX_SPLIT) the split and the vector ALUs as in the bootstrap
 hipError_t launch_embed_mx(const ScanArgs& a0, int mode, bool aligned, int grid, hipStream_t s) {
@@ -992,11 +977,16 @@ hipError_t launch_embed_mx(const ScanArgs& a0, int mode, bool aligned, int grid,
 #ifdef PSH_TUNING
     if (const char* e = getenv("PSH_DBG_TIMES_PTR")) a.dbg_times = (unsigned long long*)strtoull(e, nullptr, 0);   // tools/emx_phases.py
 #endif
-    if (mode == PSH_MODE_BOOT) return aligned ? launch_emx<true, PSH_MODE_BOOT, 3, false>(a, grid, s) : launch_emx<false, PSH_MODE_BOOT, 3, false>(a, grid, s);
-    if (a.emb_mx == 3) return aligned ? launch_emx<true, PSH_MODE_FILTER, 3, false>(a, grid, s) : launch_emx<false, PSH_MODE_FILTER, 3, false>(a, grid, s);
-    if (a.B >= PSH_EMX_QM_MIN_B && a.B <= PSH_EMX_QM_MAX_B)
-        return aligned ? launch_emx<true, PSH_MODE_FILTER, 1, true>(a, grid, s) : launch_emx<false, PSH_MODE_FILTER, 1, true>(a, grid, s);
-    return aligned ? launch_emx<true, PSH_MODE_FILTER, 1, false>(a, grid, s) : launch_emx<false, PSH_MODE_FILTER, 1, false>(a, grid, s);
+    // the four (MODE, NP, QM) that exist, by number
+    const int variant = mode == PSH_MODE_BOOT ? 0 : a.emb_mx == 3 ? 1 : (a.B >= PSH_EMX_QM_MIN_B && a.B <= PSH_EMX_QM_MAX_B) ? 2 : 3;
+    const int ng = (a.emb_d + 3) >> 2;
+    const size_t shmem = emx_shmem_bytes(a.W, a.emb_d, a.B, a.tile_floats);
+    return pick<0, 1, 2, 3>(variant, [&](auto V) {
+        constexpr int MODE = V() == 0 ? PSH_MODE_BOOT : PSH_MODE_FILTER, NP = V() <= 1 ? 3 : 1;
+        constexpr bool QM = V() == 2;
+        return pick<true, false>(aligned, [&](auto AL) {
+            return pick<1, 2, 3>(ng == 1 || ng == 2 ? ng : 3, [&](auto NG) {
+                return launch(embed_mx_kernel<AL(), MODE, NG(), NP, QM>, grid, PSH_EMX_THREADS, shmem, s, a); }); }); });
 }
 
 }  // namespace psh

@@ -31,6 +31,7 @@
 // stage does the work -- the other one returns at once.
 #include <type_traits>
 
+#include "psh_launch.h"
 #include "psh_segment.h"
 
 namespace psh {
@@ -250,13 +251,7 @@ __global__ __launch_bounds__(PSH_PLAN_THREADS) void embed_plan_kernel(const floa
 }
 
 hipError_t launch_embed_plan(const float* ker, int d, int K, EmbedPlan* plan, hipStream_t s) {
-    const size_t shmem = (size_t)d * K * sizeof(float);
-    if (shmem > 48 * 1024) {
-        const hipError_t e = hipFuncSetAttribute((const void*)embed_plan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(embed_plan_kernel, dim3(1), dim3(PSH_PLAN_THREADS), shmem, s, ker, d, K, plan);
-    return hipGetLastError();
+    return launch(embed_plan_kernel, 1, PSH_PLAN_THREADS, (size_t)d * K * sizeof(float), s, ker, d, K, plan);
 }
 
 // Exclusive prefix sums of the staged segment (element 4 (lane + 64 q) + r of Stage) -> dst[0 .. 4 nq]; returns the sum of
@@ -831,27 +826,12 @@ bool embed_px_supported(int tile_floats, int B, int d, int K, bool wide) {
            px_shmem_bytes(tile_floats, B, d, wide ? PSH_PX_WIDE_THREADS : PSH_PX_THREADS) <= PSH_LDS_BYTES;
 }
 
-template <bool ALIGNED, int MODE>
-static hipError_t launch_px_mode(const ScanArgs& a, int grid, hipStream_t s) {
-    if (a.emb_wide) {
-        const size_t shmem = px_shmem_bytes(a.tile_floats, a.B, a.emb_d, PSH_PX_WIDE_THREADS);
-        hipError_t e = hipFuncSetAttribute((const void*)embed_px_kernel<ALIGNED, MODE, PSH_PX_WIDE_THREADS, PSH_PX_WIDE_NBG>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((embed_px_kernel<ALIGNED, MODE, PSH_PX_WIDE_THREADS, PSH_PX_WIDE_NBG>), dim3(grid), dim3(PSH_PX_WIDE_THREADS), shmem, s, a);
-        return hipGetLastError();
-    }
-    const size_t shmem = px_shmem_bytes(a.tile_floats, a.B, a.emb_d, PSH_PX_THREADS);
-    hipError_t e = hipFuncSetAttribute((const void*)embed_px_kernel<ALIGNED, MODE, PSH_PX_THREADS, PSH_PX_NBG>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((embed_px_kernel<ALIGNED, MODE, PSH_PX_THREADS, PSH_PX_NBG>), dim3(grid), dim3(PSH_PX_THREADS), shmem, s, a);
-    return hipGetLastError();
-}
-
 hipError_t launch_embed_px(const ScanArgs& a, int mode, bool aligned, int grid, hipStream_t s) {
-    if (mode == PSH_MODE_BOOT) return aligned ? launch_px_mode<true, PSH_MODE_BOOT>(a, grid, s) : launch_px_mode<false, PSH_MODE_BOOT>(a, grid, s);
-    return aligned ? launch_px_mode<true, PSH_MODE_FILTER>(a, grid, s) : launch_px_mode<false, PSH_MODE_FILTER>(a, grid, s);
+    return pick<PSH_MODE_BOOT, PSH_MODE_FILTER>(mode == PSH_MODE_BOOT ? PSH_MODE_BOOT : PSH_MODE_FILTER, [&](auto MODE) {
+        return pick<true, false>(aligned, [&](auto AL) {
+            return pick<true, false>(a.emb_wide != 0, [&](auto WIDE) {
+                constexpr int THREADS = WIDE() ? PSH_PX_WIDE_THREADS : PSH_PX_THREADS, NBG = WIDE() ? PSH_PX_WIDE_NBG : PSH_PX_NBG;
+                return launch(embed_px_kernel<AL(), MODE(), THREADS, NBG>, grid, THREADS, px_shmem_bytes(a.tile_floats, a.B, a.emb_d, THREADS), s, a); }); }); });
 }
 
 }  // namespace psh

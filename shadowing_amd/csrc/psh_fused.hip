@@ -32,6 +32,7 @@
 // (|y~| > 255) has acc~ >= (255 - 8)^2 > tau~ and is rightly rejected when its t^ comes out +inf (NaN is kept).
 // Both follow from the query and tau alone: scale = the largest power of two with max|x| * scale < 8 and
 // tau2 * scale^2 <= 4096.
+#include "psh_launch.h"
 #include "psh_segment.h"
 
 namespace psh {
@@ -696,28 +697,12 @@ size_t scan_fused_shmem_bytes(int tile_floats) {
            + (size_t)(PSH_SCAN_THREADS / 64) * 2 * PSH_MX_NHALF * sizeof(_Float16);
 }
 
-template <typename K>
-static hipError_t launch_fused_k(K kernel, int grid, size_t shmem, hipStream_t s, const ScanArgs& a, const FusedArgs& f) {
-    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(PSH_SCAN_THREADS), shmem, s, a, f);
-    return hipGetLastError();
-}
-
-template <bool HINTED, bool BLK>
-static hipError_t launch_fused_hb(const ScanArgs& a, const FusedArgs& f, bool aligned, int grid, size_t shmem, hipStream_t s) {
-    if (a.W == 20)
-        return aligned ? launch_fused_k(scan_fused_kernel<20, true, HINTED, BLK>, grid, shmem, s, a, f)
-                       : launch_fused_k(scan_fused_kernel<20, false, HINTED, BLK>, grid, shmem, s, a, f);
-    return aligned ? launch_fused_k(scan_fused_kernel<0, true, HINTED, BLK>, grid, shmem, s, a, f)
-                   : launch_fused_k(scan_fused_kernel<0, false, HINTED, BLK>, grid, shmem, s, a, f);
-}
-
 hipError_t launch_scan_fused(const ScanArgs& a, const FusedArgs& f, bool aligned, int grid, hipStream_t s) {
     const size_t shmem = scan_fused_shmem_bytes(a.tile_floats);
-    const bool blk = f.g_ds != nullptr && f.done != nullptr;
-    if (f.tau_hint) return blk ? launch_fused_hb<true, true>(a, f, aligned, grid, shmem, s) : launch_fused_hb<true, false>(a, f, aligned, grid, shmem, s);
-    return blk ? launch_fused_hb<false, true>(a, f, aligned, grid, shmem, s) : launch_fused_hb<false, false>(a, f, aligned, grid, shmem, s);
+    return pick<true, false>(f.tau_hint != nullptr, [&](auto HINTED) {
+        return pick<true, false>(f.g_ds != nullptr && f.done != nullptr, [&](auto BLK) {
+            return pick_w_aligned(a.W, aligned, [&](auto WT, auto AL) {
+                return launch(scan_fused_kernel<WT(), AL(), HINTED(), BLK()>, grid, PSH_SCAN_THREADS, shmem, s, a, f); }); }); });
 }
 
 }  // namespace psh

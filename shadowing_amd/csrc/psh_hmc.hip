@@ -53,6 +53,7 @@
 // block inverts Black-Scholes by the same bisection as pricing.py.  No workspace.  The status words are zeroed on the
 // stream before the launch and OR-ed by the g == 0 block of each (date, maturity), whichever finishes first.
 // The body lives in psh_hmc_body.h, which psh_hmc_report.hip instantiates a second time with the policy kept.
+#include "psh_launch.h"
 #include "psh_hmc_body.h"
 
 namespace psh {
@@ -69,24 +70,7 @@ hipError_t launch_hedged_mc(const HmcArgs& a, hipStream_t s) {
         const hipError_t e = hipMemsetAsync(a.status, 0, (size_t)a.B * sizeof(int32_t), s);
         if (e != hipSuccess) return e;
     }
-#define PSH_HMC_CASE(P)                                                                                          \
-    case P: {                                                                                                    \
-        hipError_t e = hipFuncSetAttribute((const void*)hmc_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                           (int)shmem);                                                          \
-        if (e != hipSuccess) return e;                                                                           \
-        hipLaunchKernelGGL(hmc_kernel<P>, grid, block, shmem, s, a);                                             \
-        break;                                                                                                   \
-    }
-    switch (a.degree) {
-        PSH_HMC_CASE(1)
-        PSH_HMC_CASE(2)
-        PSH_HMC_CASE(3)
-        PSH_HMC_CASE(4)
-        PSH_HMC_CASE(5)
-        default: return hipErrorInvalidValue;
-    }
-#undef PSH_HMC_CASE
-    return hipGetLastError();
+    return pick<1, 2, 3, 4, 5>(a.degree, [&](auto P) { return launch(hmc_kernel<P()>, grid, block, shmem, s, a); });
 }
 
 }  // namespace psh

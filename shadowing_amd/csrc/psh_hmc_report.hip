@@ -44,6 +44,7 @@
 //   tutorial case (L = 252, Ts 7/25/75)   B = 1: fit 4.00  policy 3.89  replay 0.099 / 0.100;  B = 64: 8.43  8.43  1.399 / 1.409
 // The policy variant costs nothing this measurement can see (one store of 2P + 4 doubles per step by <= 3 lanes, and a
 // memset); the replay is 3 % to 17 % of the fit.
+#include "psh_launch.h"
 #include "psh_hmc_body.h"
 
 namespace psh {
@@ -64,24 +65,7 @@ hipError_t launch_hedged_mc_policy(const HmcArgs& a, double* policy, hipStream_t
         e = hipMemsetAsync(a.status, 0, (size_t)a.B * sizeof(int32_t), s);
         if (e != hipSuccess) return e;
     }
-#define PSH_HMC_CASE(P)                                                                                          \
-    case P: {                                                                                                    \
-        e = hipFuncSetAttribute((const void*)hmc_policy_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                (int)shmem);                                                                     \
-        if (e != hipSuccess) return e;                                                                           \
-        hipLaunchKernelGGL(hmc_policy_kernel<P>, grid, block, shmem, s, a, policy);                              \
-        break;                                                                                                   \
-    }
-    switch (a.degree) {
-        PSH_HMC_CASE(1)
-        PSH_HMC_CASE(2)
-        PSH_HMC_CASE(3)
-        PSH_HMC_CASE(4)
-        PSH_HMC_CASE(5)
-        default: return hipErrorInvalidValue;
-    }
-#undef PSH_HMC_CASE
-    return hipGetLastError();
+    return pick<1, 2, 3, 4, 5>(a.degree, [&](auto P) { return launch(hmc_policy_kernel<P()>, grid, block, shmem, s, a, policy); });
 }
 
 namespace {
@@ -246,27 +230,9 @@ hipError_t launch_hedge_replay(const HedgeReplayArgs& a, hipStream_t s) {
         e = hipMemsetAsync(a.status, 0, (size_t)a.B * sizeof(int32_t), s);
         if (e != hipSuccess) return e;
     }
-#define PSH_HEDGE_CASE(P)                                                                                          \
-    case P: {                                                                                                      \
-        e = hipFuncSetAttribute((const void*)hedge_replay_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                (int)shmem);                                                                       \
-        if (e != hipSuccess) return e;                                                                             \
-        hipLaunchKernelGGL(hedge_replay_kernel<P>, grid, block, shmem, s, a);                                      \
-        break;                                                                                                     \
-    }
-    switch (a.degree) {
-        PSH_HEDGE_CASE(1)
-        PSH_HEDGE_CASE(2)
-        PSH_HEDGE_CASE(3)
-        PSH_HEDGE_CASE(4)
-        PSH_HEDGE_CASE(5)
-        default: return hipErrorInvalidValue;
-    }
-#undef PSH_HEDGE_CASE
-    e = hipGetLastError();
+    e = pick<1, 2, 3, 4, 5>(a.degree, [&](auto P) { return launch(hedge_replay_kernel<P()>, grid, block, shmem, s, a); });
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(hedge_finish_kernel, dim3((unsigned)((int64_t)a.B * a.nT * a.nM)), dim3(64), 0, s, a);
-    return hipGetLastError();
+    return launch(hedge_finish_kernel, (unsigned)((int64_t)a.B * a.nT * a.nM), 64, 0, s, a);
 }
 
 }  // namespace psh

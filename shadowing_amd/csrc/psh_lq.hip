@@ -20,6 +20,7 @@
 // The launches around it are the separate launches' (psh_capi.hip): bootstrap -> threshold_kernel -> scan -> select_kernel.
 // Results are the exact top-k: what is ranked is always the sequential fp32 chain (include/psh.h).
 #include <type_traits>
+#include "psh_launch.h"
 #include "psh_segment.h"
 
 namespace psh {
@@ -471,27 +472,12 @@ size_t scan_lq_shmem_bytes(int W, int B, int q_per_group) {
     return (size_t)PSH_LQ_FIXED + (size_t)q_per_group * lq_query_bytes(nks) + (size_t)(PSH_LQ_THREADS / 64) * lq_wave_bytes(nks);
 }
 
-template <int MODE>
-static hipError_t launch_lq_m(const ScanArgs& a, int grid_x, hipStream_t s) {
-    const int nks = lq_bucket(a.W);
+hipError_t launch_scan_lq(const ScanArgs& a, int mode, int grid_x, hipStream_t s) {
     const size_t shmem = scan_lq_shmem_bytes(a.W, a.B, a.q_per_group);
     const dim3 grid((unsigned)grid_x, (unsigned)a.n_qgroups);
-#define PSH_LQ_LAUNCH(KERNEL)                                                                                                        \
-    {                                                                                                                                \
-        hipError_t e = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);             \
-        if (e != hipSuccess) return e;                                                                                               \
-        hipLaunchKernelGGL(KERNEL, grid, dim3(PSH_LQ_THREADS), shmem, s, a);                                                         \
-        return hipGetLastError();                                                                                                    \
-    }
-    if (nks == 6) PSH_LQ_LAUNCH((scan_lq_kernel<MODE, 6>))
-    if (nks == 10) PSH_LQ_LAUNCH((scan_lq_kernel<MODE, 10>))
-    if (nks == 14) PSH_LQ_LAUNCH((scan_lq_kernel<MODE, 14>))
-    PSH_LQ_LAUNCH((scan_lq_kernel<MODE, 18>))
-#undef PSH_LQ_LAUNCH
-}
-
-hipError_t launch_scan_lq(const ScanArgs& a, int mode, int grid_x, hipStream_t s) {
-    return mode == PSH_MODE_BOOT ? launch_lq_m<PSH_MODE_BOOT>(a, grid_x, s) : launch_lq_m<PSH_MODE_FILTER>(a, grid_x, s);
+    return pick<PSH_MODE_BOOT, PSH_MODE_FILTER>(mode == PSH_MODE_BOOT ? PSH_MODE_BOOT : PSH_MODE_FILTER, [&](auto MODE) {
+        return pick<6, 10, 14, 18>(lq_bucket(a.W), [&](auto NKS) {
+            return launch(scan_lq_kernel<MODE(), NKS()>, grid, PSH_LQ_THREADS, shmem, s, a); }); });
 }
 
 }  // namespace psh

@@ -36,6 +36,7 @@
 //     part; 5e4 of them were 5x the whole scan).  A one-block radix select then picks the
 //     k best and orders them by (d, r, t).
 //   * the embedded scan (embed_scan_kernel) runs the same pipeline behind a linear embedding.
+#include "psh_launch.h"
 #include "psh_segment.h"
 
 namespace psh {
@@ -1375,54 +1376,12 @@ __global__ __launch_bounds__(PSH_MQ_THREADS) void boot_mq_kernel(ScanArgs a) {
 // ----------------------------------------------------------------------------------
 // launchers (host)
 // ----------------------------------------------------------------------------------
-template <int WT, bool ALIGNED, int MODE>
-static hipError_t allow_big_lds(size_t shmem) {
-    if (shmem <= 48 * 1024) return hipSuccess;
-    return hipFuncSetAttribute((const void*)scan_kernel<WT, ALIGNED, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-}
-
-template <int WT, bool ALIGNED>
-static hipError_t launch_scan_mode(const ScanArgs& a, int mode, int grid, size_t shmem, hipStream_t s) {
-    hipError_t e = mode == PSH_MODE_BOOT ? allow_big_lds<WT, ALIGNED, PSH_MODE_BOOT>(shmem)
-                 : mode == PSH_MODE_FILTER ? allow_big_lds<WT, ALIGNED, PSH_MODE_FILTER>(shmem)
-                                           : allow_big_lds<WT, ALIGNED, PSH_MODE_ALL>(shmem);
-    if (e != hipSuccess) return e;
-    switch (mode) {
-        case PSH_MODE_BOOT:
-            hipLaunchKernelGGL((scan_kernel<WT, ALIGNED, PSH_MODE_BOOT>), dim3(grid), dim3(PSH_SCAN_THREADS), shmem, s, a);
-            break;
-        case PSH_MODE_FILTER:
-            hipLaunchKernelGGL((scan_kernel<WT, ALIGNED, PSH_MODE_FILTER>), dim3(grid), dim3(PSH_SCAN_THREADS), shmem, s, a);
-            break;
-        default:
-            hipLaunchKernelGGL((scan_kernel<WT, ALIGNED, PSH_MODE_ALL>), dim3(grid), dim3(PSH_SCAN_THREADS), shmem, s, a);
-            break;
-    }
-    return hipGetLastError();
-}
-
 bool scan_mx_supported(int W, int B) { return W >= 1 && W <= 33 && B == 1; }
 
 size_t scan_mx_shmem_bytes(int tile_floats, int /*B*/) {
     return (size_t)tile_floats * (PSH_SCAN_THREADS / 64) * sizeof(float) + 32
            + (size_t)(PSH_SCAN_THREADS / 64) * PSH_MX_PEND * 16
            + (size_t)(PSH_SCAN_THREADS / 64) * 2 * PSH_MX_NHALF * sizeof(_Float16);
-}
-
-// launch a <WT, ALIGNED> kernel family member: W = 20 has its own instantiation, other lengths run WT = 0
-template <typename K>
-static hipError_t launch_big_lds(K kernel, dim3 grid, int threads, size_t shmem, hipStream_t s, const ScanArgs& a) {
-    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, grid, dim3(threads), shmem, s, a);
-    return hipGetLastError();
-}
-
-template <bool ALIGNED>
-static hipError_t launch_scan_mx(const ScanArgs& a, int grid, hipStream_t s) {
-    const size_t shmem = scan_mx_shmem_bytes(a.tile_floats, a.B);
-    return a.W == 20 ? launch_big_lds(scan_mx_kernel<20, ALIGNED>, dim3(grid), PSH_SCAN_THREADS, shmem, s, a)
-                     : launch_big_lds(scan_mx_kernel<0, ALIGNED>, dim3(grid), PSH_SCAN_THREADS, shmem, s, a);
 }
 
 bool scan_mq_supported(int W, int B) { return W >= 1 && W <= 25 && B >= 2; }
@@ -1447,58 +1406,33 @@ size_t boot_mq_shmem_bytes(int tile_floats) {
 }
 
 hipError_t launch_boot_mq(const ScanArgs& a, bool aligned, int grid_x, hipStream_t s) {
-    const size_t shmem = boot_mq_shmem_bytes(a.tile_floats);
-    const dim3 grid(grid_x, boot_mq_chunks(a.B));
-    if (a.W == 20)
-        return aligned ? launch_big_lds(boot_mq_kernel<20, true>, grid, PSH_MQ_THREADS, shmem, s, a)
-                       : launch_big_lds(boot_mq_kernel<20, false>, grid, PSH_MQ_THREADS, shmem, s, a);
-    return aligned ? launch_big_lds(boot_mq_kernel<0, true>, grid, PSH_MQ_THREADS, shmem, s, a)
-                   : launch_big_lds(boot_mq_kernel<0, false>, grid, PSH_MQ_THREADS, shmem, s, a);
+    return pick_w_aligned(a.W, aligned, [&](auto WT, auto AL) {
+        return launch(boot_mq_kernel<WT(), AL()>, dim3(grid_x, boot_mq_chunks(a.B)), PSH_MQ_THREADS, boot_mq_shmem_bytes(a.tile_floats), s, a); });
 }
 
 hipError_t launch_scan_mq(const ScanArgs& a, bool aligned, int grid_x, hipStream_t s) {
     const size_t shmem = scan_mq_shmem_bytes(a.tile_floats, a.B);
     const dim3 grid(grid_x, scan_mq_chunks(a.B));
-    if (a.mq_i8) {
-        if (a.W == 20)
-            return aligned ? launch_big_lds(scan_mq8_kernel<20, true>, grid, PSH_MQ_THREADS, shmem, s, a)
-                           : launch_big_lds(scan_mq8_kernel<20, false>, grid, PSH_MQ_THREADS, shmem, s, a);
-        return aligned ? launch_big_lds(scan_mq8_kernel<0, true>, grid, PSH_MQ_THREADS, shmem, s, a)
-                       : launch_big_lds(scan_mq8_kernel<0, false>, grid, PSH_MQ_THREADS, shmem, s, a);
-    }
-    if (a.W == 20)
-        return aligned ? launch_big_lds(scan_mq_kernel<20, true>, grid, PSH_MQ_THREADS, shmem, s, a)
-                       : launch_big_lds(scan_mq_kernel<20, false>, grid, PSH_MQ_THREADS, shmem, s, a);
-    return aligned ? launch_big_lds(scan_mq_kernel<0, true>, grid, PSH_MQ_THREADS, shmem, s, a)
-                   : launch_big_lds(scan_mq_kernel<0, false>, grid, PSH_MQ_THREADS, shmem, s, a);
+    return pick_w_aligned(a.W, aligned, [&](auto WT, auto AL) {
+        return a.mq_i8 ? launch(scan_mq8_kernel<WT(), AL()>, grid, PSH_MQ_THREADS, shmem, s, a)
+                       : launch(scan_mq_kernel<WT(), AL()>, grid, PSH_MQ_THREADS, shmem, s, a); });
 }
 
 hipError_t launch_scan(const ScanArgs& a, int mode, bool aligned, int grid, hipStream_t s) {
     if (a.ker) return launch_embed_scan(a, mode, aligned, grid, s);           // psh_embed.hip
-    const size_t shmem = scan_shmem_bytes(a.tile_floats, a.B, 0, a.W, PSH_SCAN_THREADS);
-    if (a.use_mx && mode == PSH_MODE_FILTER && scan_mx_supported(a.W, a.B))
-        return aligned ? launch_scan_mx<true>(a, grid, s) : launch_scan_mx<false>(a, grid, s);
-    if (a.W == 20) {
-        return aligned ? launch_scan_mode<20, true>(a, mode, grid, shmem, s)
-                       : launch_scan_mode<20, false>(a, mode, grid, shmem, s);
-    }
-    return aligned ? launch_scan_mode<0, true>(a, mode, grid, shmem, s)
-                   : launch_scan_mode<0, false>(a, mode, grid, shmem, s);
+    const bool mx = a.use_mx && mode == PSH_MODE_FILTER && scan_mx_supported(a.W, a.B);
+    const size_t shmem = mx ? scan_mx_shmem_bytes(a.tile_floats, a.B) : scan_shmem_bytes(a.tile_floats, a.B, 0, a.W, PSH_SCAN_THREADS);
+    return pick_w_aligned(a.W, aligned, [&](auto WT, auto AL) {
+        if (mx) return launch(scan_mx_kernel<WT(), AL()>, grid, PSH_SCAN_THREADS, shmem, s, a);
+        return pick<PSH_MODE_BOOT, PSH_MODE_FILTER, PSH_MODE_ALL>(mode == PSH_MODE_BOOT || mode == PSH_MODE_FILTER ? mode : PSH_MODE_ALL, [&](auto MODE) {
+            return launch(scan_kernel<WT(), AL(), MODE()>, grid, PSH_SCAN_THREADS, shmem, s, a); }); });
 }
 
 hipError_t scan_blocks_per_cu(int W, bool aligned, bool embedded, size_t shmem, int* out) {
     if (embedded) return embed_blocks_per_cu(aligned, shmem, out);              // psh_embed.hip
-    int n = 0;
-    hipError_t e;
-    if (W == 20) {
-        e = aligned ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, scan_kernel<20, true, PSH_MODE_FILTER>, PSH_SCAN_THREADS, shmem)
-                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, scan_kernel<20, false, PSH_MODE_FILTER>, PSH_SCAN_THREADS, shmem);
-    } else {
-        e = aligned ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, scan_kernel<0, true, PSH_MODE_FILTER>, PSH_SCAN_THREADS, shmem)
-                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, scan_kernel<0, false, PSH_MODE_FILTER>, PSH_SCAN_THREADS, shmem);
-    }
-    *out = n;
-    return e;
+    *out = 0;
+    return pick_w_aligned(W, aligned, [&](auto WT, auto AL) {
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(out, scan_kernel<WT(), AL(), PSH_MODE_FILTER>, PSH_SCAN_THREADS, shmem); });
 }
 
 }  // namespace psh

@@ -2,6 +2,7 @@
 // final top-k selection and ordering, merge of per-shard lists, path gather; with their launchers.  Part of
 // libpsh_hip.so; shared device code in psh_device.h, design overview at the top of psh_scan.hip.
 #include "psh_device.h"
+#include "psh_launch.h"
 
 namespace psh {
 
@@ -1361,24 +1362,17 @@ __global__ void gather_kernel(GatherArgs a) {
 
 
 hipError_t launch_prep(const PrepArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(prep_kernel, dim3(a.B), dim3(64), 0, s, a);
-    return hipGetLastError();
+    return launch(prep_kernel, a.B, 64, 0, s, a);
 }
 hipError_t launch_qnorm(const float* q, int B, int W, float* out, hipStream_t s) {
-    hipLaunchKernelGGL(qnorm_kernel, dim3((B + 63) / 64), dim3(64), 0, s, q, B, W, out);
-    return hipGetLastError();
+    return launch(qnorm_kernel, (B + 63) / 64, 64, 0, s, q, B, W, out);
 }
 hipError_t launch_threshold(const ThresholdArgs& a0, int B, hipStream_t s) {
     ThresholdArgs a = a0;
     size_t shmem = (size_t)a.n_entries * sizeof(unsigned);
     a.keys_in_lds = shmem <= 128 * 1024;
     if (!a.keys_in_lds) shmem = 0;
-    if (shmem > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)threshold_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(threshold_kernel, dim3(B), dim3(PSH_SELECT_THREADS), shmem, s, a);
-    return hipGetLastError();
+    return launch(threshold_kernel, B, PSH_SELECT_THREADS, shmem, s, a);
 }
 hipError_t launch_select(const SelectArgs& a0, int B, hipStream_t s) {
     SelectArgs a = a0;
@@ -1402,10 +1396,6 @@ hipError_t launch_select(const SelectArgs& a0, int B, hipStream_t s) {
     if (!a.rank_sort && (a.sort_buf_ok || a.kpad <= 8 * PSH_SELECT_THREADS || (int64_t)a.cand_stride < (int64_t)a.kpad)) a.sort_scratch = nullptr;
     if (a.sort_buf_ok && area < 2 * (int64_t)a.kpad) area = 2 * (int64_t)a.kpad;
     const size_t shmem = items_bytes + (size_t)area * sizeof(unsigned);
-    if (shmem > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (e != hipSuccess) return e;
-    }
     // up to 8 queries with few candidates expected: the ranking on all CUs first (rank_select_kernel), 256 blocks for one or two
     // queries, 256 / B for more (a block's own share stays within PSH_RANK_OWN down to 16 blocks)
     if (a.handled) {
@@ -1414,40 +1404,28 @@ hipError_t launch_select(const SelectArgs& a0, int B, hipStream_t s) {
         if (a.bcount && B <= PSH_RANK_MAX_B && a.k <= PSH_RANK_CAP / 2 && !a.skip_negative_rows && a.rank_tbits >= 0) {
             int G = PSH_RANK_GRID;
             if (B > 2) { G = PSH_RANK_GRID / B; if (G < 16) G = 16; }
-            hipLaunchKernelGGL(rank_select_kernel, dim3(G, B), dim3(PSH_SELECT_THREADS), 0, s, a);
+            const hipError_t e = launch(rank_select_kernel, dim3(G, B), PSH_SELECT_THREADS, 0, s, a);
+            if (e != hipSuccess) return e;
         } else
             a.handled = nullptr;
     }
-    hipLaunchKernelGGL(select_kernel, dim3(B), dim3(PSH_SELECT_THREADS), shmem, s, a);
-    if (a.rank_sort) {
-        const size_t ms_shmem = (size_t)a.kpad * sizeof(unsigned);
-        if (ms_shmem > 48 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)chunk_merge_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ms_shmem);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(chunk_sort_kernel, dim3(a.kpad / PSH_CHUNK, B), dim3(PSH_CHUNK), 0, s, a);
-        hipLaunchKernelGGL(chunk_merge_kernel, dim3(a.kpad / PSH_CHUNK, B), dim3(PSH_CHUNK), ms_shmem, s, a);
-    }
-    return hipGetLastError();
+    hipError_t e = launch(select_kernel, B, PSH_SELECT_THREADS, shmem, s, a);
+    if (e != hipSuccess || !a.rank_sort) return e;
+    const dim3 chunks(a.kpad / PSH_CHUNK, B);
+    e = launch(chunk_sort_kernel, chunks, PSH_CHUNK, 0, s, a);
+    if (e != hipSuccess) return e;
+    return launch(chunk_merge_kernel, chunks, PSH_CHUNK, (size_t)a.kpad * sizeof(unsigned), s, a);
 }
 hipError_t launch_merge_sorted(const MergeSortedArgs& a, int B, hipStream_t s) {
-    const size_t shmem = (size_t)a.G * a.k_in * sizeof(unsigned);
-    if (shmem > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)merge_sorted_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(merge_sorted_kernel, dim3(B), dim3(PSH_SELECT_THREADS), shmem, s, a);
-    return hipGetLastError();
+    return launch(merge_sorted_kernel, B, PSH_SELECT_THREADS, (size_t)a.G * a.k_in * sizeof(unsigned), s, a);
 }
 hipError_t launch_reseed(const ReseedArgs& a, int B, hipStream_t s) {
-    hipLaunchKernelGGL(reseed_kernel, dim3((a.k + 255) / 256, B), dim3(256), 0, s, a);
-    return hipGetLastError();
+    return launch(reseed_kernel, dim3((a.k + 255) / 256, B), 256, 0, s, a);
 }
 hipError_t launch_gather(const GatherArgs& a, hipStream_t s) {
     const int64_t total = a.n * a.C * a.len;
     if (total <= 0) return hipSuccess;
-    hipLaunchKernelGGL(gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
-    return hipGetLastError();
+    return launch(gather_kernel, (unsigned)((total + 255) / 256), 256, 0, s, a);
 }
 
 

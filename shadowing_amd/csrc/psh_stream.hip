@@ -26,6 +26,7 @@
 // fragments and a threshold test, so a batch of 2 or 3 costs little more than one query, where the batched scan
 // (scan_mq_kernel: 8 waves per CU, sized for hundreds of queries) streams at half rate.  One f16 scale serves all queries of
 // the step: the largest that every query's proof allows (each query bounds it from above by its own max|x| and tau2).
+#include "psh_launch.h"
 #include "psh_segment.h"
 
 namespace psh {
@@ -1206,94 +1207,48 @@ size_t stream_sample_shmem_bytes(int tile_floats) {
     return t > h ? t : h;
 }
 
-template <typename K>
-static hipError_t launch_k(K kernel, dim3 grid, int threads, size_t shmem, hipStream_t s, const ScanArgs& a, const FusedArgs& f) {
-    if (shmem > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kernel, grid, dim3(threads), shmem, s, a, f);
-    return hipGetLastError();
-}
-
-template <int NWP>
-static hipError_t launch_stream_sample_w(const ScanArgs& b, const FusedArgs& f, bool aligned, int grid, size_t shmem, hipStream_t s) {
-    if (b.W == 20)
-        return aligned ? launch_k(stream_sample_kernel<20, true, NWP>, dim3(grid), 64 * NWP, shmem, s, b, f)
-                       : launch_k(stream_sample_kernel<20, false, NWP>, dim3(grid), 64 * NWP, shmem, s, b, f);
-    return aligned ? launch_k(stream_sample_kernel<0, true, NWP>, dim3(grid), 64 * NWP, shmem, s, b, f)
-                   : launch_k(stream_sample_kernel<0, false, NWP>, dim3(grid), 64 * NWP, shmem, s, b, f);
-}
 // grid: one-wave blocks for one query (they have to fit beside another step's scan), a quarter as many four-wave blocks for two
 // or three
 hipError_t launch_stream_sample(const ScanArgs& a, const FusedArgs& f, bool aligned, int grid, int sample_tile_floats, hipStream_t s) {
     ScanArgs b = a;
     b.tile_floats = sample_tile_floats;
-    if (f.nq == 1) return launch_stream_sample_w<1>(b, f, aligned, grid, stream_sample_shmem_bytes(sample_tile_floats), s);
-    return launch_stream_sample_w<4>(b, f, aligned, (grid + 3) / 4, 4 * stream_sample_shmem_bytes(sample_tile_floats), s);
+    return pick<1, 4>(f.nq == 1 ? 1 : 4, [&](auto NWP) {
+        return pick_w_aligned(b.W, aligned, [&](auto WT, auto AL) {
+            return launch(stream_sample_kernel<WT(), AL(), NWP()>, (grid + NWP() - 1) / NWP(), 64 * NWP(),
+                          NWP() * stream_sample_shmem_bytes(sample_tile_floats), s, b, f); }); });
 }
 
 size_t stream_sample_long_shmem_bytes(int W, int nq) {
     const int nks = lq_bucket(W), nwp = nq == 1 ? 1 : 4;
     return 64 + (size_t)nq * lq_query_bytes(nks) + (size_t)nwp * ((size_t)PSH_LONG_SFLOATS * 4 + (size_t)lq_rows(nks) * PSH_LONG_ROW * 2);
 }
-static hipError_t launch_stream_sample_long_1(const ScanArgs& a, const FusedArgs& f, int grid, hipStream_t s) {
-    const int nks = lq_bucket(a.W);
-    const size_t shmem = stream_sample_long_shmem_bytes(a.W, f.nq);
-    if (nks == 6) return launch_k(stream_sample_long_kernel1<6>, dim3(grid), 64, shmem, s, a, f);
-    if (nks == 10) return launch_k(stream_sample_long_kernel1<10>, dim3(grid), 64, shmem, s, a, f);
-    if (nks == 14) return launch_k(stream_sample_long_kernel1u<14>, dim3(grid), 64, shmem, s, a, f);
-    return launch_k(stream_sample_long_kernel1u<18>, dim3(grid), 64, shmem, s, a, f);
-}
-static hipError_t launch_stream_sample_long_4(const ScanArgs& a, const FusedArgs& f, int grid, hipStream_t s) {
-    const int nks = lq_bucket(a.W);
-    const size_t shmem = stream_sample_long_shmem_bytes(a.W, f.nq);
-    if (nks == 6) return launch_k(stream_sample_long_kernel4<6>, dim3(grid), 256, shmem, s, a, f);
-    if (nks == 10) return launch_k(stream_sample_long_kernel4<10>, dim3(grid), 256, shmem, s, a, f);
-    if (nks == 14) return launch_k(stream_sample_long_kernel4<14>, dim3(grid), 256, shmem, s, a, f);
-    return launch_k(stream_sample_long_kernel4<18>, dim3(grid), 256, shmem, s, a, f);
-}
 // the long-window step's sample (34 <= W <= 256, no hint): one-wave blocks for one query, a quarter as many four-wave blocks for
 // two or three (launch_stream_sample's rule)
 hipError_t launch_stream_sample_long(const ScanArgs& a, const FusedArgs& f, int grid, hipStream_t s) {
-    if (f.nq == 1) return launch_stream_sample_long_1(a, f, grid, s);
-    return launch_stream_sample_long_4(a, f, (grid + 3) / 4, s);
+    const size_t shmem = stream_sample_long_shmem_bytes(a.W, f.nq);
+    return pick<6, 10, 14, 18>(lq_bucket(a.W), [&](auto NKS) {
+        if (f.nq != 1) return launch(stream_sample_long_kernel4<NKS()>, (grid + 3) / 4, 256, shmem, s, a, f);
+        if constexpr (NKS() <= 10) return launch(stream_sample_long_kernel1<NKS()>, grid, 64, shmem, s, a, f);
+        else return launch(stream_sample_long_kernel1u<NKS()>, grid, 64, shmem, s, a, f); });
 }
 
-template <int NQ>
-static hipError_t launch_stream_scan_q(const ScanArgs& a, const FusedArgs& f, bool aligned, int grid, hipStream_t s) {
-    const size_t shmem = stream_scan_shmem_bytes_q(a.tile_floats, NQ);
-    if (a.W == 20)
-        return aligned ? launch_k(stream_scan_q_kernel<20, true, NQ>, dim3(grid), PSH_SCAN_THREADS, shmem, s, a, f)
-                       : launch_k(stream_scan_q_kernel<20, false, NQ>, dim3(grid), PSH_SCAN_THREADS, shmem, s, a, f);
-    return aligned ? launch_k(stream_scan_q_kernel<0, true, NQ>, dim3(grid), PSH_SCAN_THREADS, shmem, s, a, f)
-                   : launch_k(stream_scan_q_kernel<0, false, NQ>, dim3(grid), PSH_SCAN_THREADS, shmem, s, a, f);
-}
 hipError_t launch_stream_scan(const ScanArgs& a, const FusedArgs& f, bool aligned, int grid, hipStream_t s) {
-    if (f.nq == 2) return launch_stream_scan_q<2>(a, f, aligned, grid, s);
-    if (f.nq == 3) return launch_stream_scan_q<3>(a, f, aligned, grid, s);
-    const size_t shmem = stream_scan_shmem_bytes_q(a.tile_floats, 1);
-    if (a.W == 20)
-        return aligned ? launch_k(stream_scan_kernel<20, true>, dim3(grid), PSH_SCAN_THREADS, shmem, s, a, f)
-                       : launch_k(stream_scan_kernel<20, false>, dim3(grid), PSH_SCAN_THREADS, shmem, s, a, f);
-    return aligned ? launch_k(stream_scan_kernel<0, true>, dim3(grid), PSH_SCAN_THREADS, shmem, s, a, f)
-                   : launch_k(stream_scan_kernel<0, false>, dim3(grid), PSH_SCAN_THREADS, shmem, s, a, f);
+    return pick<1, 2, 3>(f.nq == 2 || f.nq == 3 ? f.nq : 1, [&](auto NQ) {
+        const size_t shmem = stream_scan_shmem_bytes_q(a.tile_floats, NQ());
+        return pick_w_aligned(a.W, aligned, [&](auto WT, auto AL) {
+            if constexpr (NQ() == 1) return launch(stream_scan_kernel<WT(), AL()>, grid, PSH_SCAN_THREADS, shmem, s, a, f);
+            else return launch(stream_scan_q_kernel<WT(), AL(), NQ()>, grid, PSH_SCAN_THREADS, shmem, s, a, f); }); });
 }
 
-template <int NQ>
-static hipError_t launch_stream_scan_long_q(const ScanArgs& a, const FusedArgs& f, bool aligned, int grid, hipStream_t s) {
-    const size_t shmem = stream_scan_long_shmem_bytes(a.W, NQ);
-    return aligned ? launch_k(stream_scan_long_kernel<true, NQ>, dim3(grid), PSH_SCAN_THREADS, shmem, s, a, f)
-                   : launch_k(stream_scan_long_kernel<false, NQ>, dim3(grid), PSH_SCAN_THREADS, shmem, s, a, f);
-}
 hipError_t launch_stream_scan_long(const ScanArgs& a, const FusedArgs& f, bool aligned, int grid, hipStream_t s) {
-    return f.nq == 1 ? launch_stream_scan_long_q<1>(a, f, aligned, grid, s)
-         : f.nq == 2 ? launch_stream_scan_long_q<2>(a, f, aligned, grid, s) : launch_stream_scan_long_q<3>(a, f, aligned, grid, s);
+    return pick<1, 2, 3>(f.nq == 1 || f.nq == 2 ? f.nq : 3, [&](auto NQ) {
+        return pick<true, false>(aligned, [&](auto AL) {
+            return launch(stream_scan_long_kernel<AL(), NQ()>, grid, PSH_SCAN_THREADS, stream_scan_long_shmem_bytes(a.W, NQ()), s, a, f); }); });
 }
 
 hipError_t launch_stream_rank(const ScanArgs& a, const FusedArgs& f, int grid, hipStream_t s) {
-    return f.tbits >= 0 ? launch_k(stream_rank_kernel<true>, dim3(grid, f.nq), 64, 0, s, a, f)
-                        : launch_k(stream_rank_kernel<false>, dim3(grid, f.nq), 64, 0, s, a, f);
+    return pick<true, false>(f.tbits >= 0, [&](auto HINTED) {
+        return launch(stream_rank_kernel<HINTED()>, dim3(grid, f.nq), 64, 0, s, a, f); });
 }
 
 }  // namespace psh

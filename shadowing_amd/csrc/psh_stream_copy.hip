@@ -56,6 +56,7 @@
 // mismatch -- the copy is of other data than the ensemble -- sets StreamCtl::ovf: the ranking reports PSH_STATUS_RETRY and the
 // caller reruns through the separate launches and drops the copy.  Only survivors are audited: a copy of another ensemble is
 // caught at once, a sparse edit the caller hid from the copy's owner may not be.
+#include "psh_launch.h"
 #include "psh_segment.h"
 
 namespace psh {
@@ -455,16 +456,8 @@ size_t copy_scan_shmem_bytes(int tile_floats) {
 }
 
 hipError_t launch_copy_scan(const ScanArgs& a, const FusedArgs& f, const CopyArgs& cp, int grid, hipStream_t s) {
-    const size_t shmem = copy_scan_shmem_bytes(a.tile_floats);
-    auto go = [&](auto kernel) -> hipError_t {
-        if (shmem > 48 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(PSH_SCAN_THREADS), shmem, s, a, f, cp);
-        return hipGetLastError();
-    };
-    return a.W == 20 ? go(copy_scan_kernel<20>) : go(copy_scan_kernel<0>);
+    return pick<20, 0>(a.W == 20 ? 20 : 0, [&](auto WT) {
+        return launch(copy_scan_kernel<WT()>, grid, PSH_SCAN_THREADS, copy_scan_shmem_bytes(a.tile_floats), s, a, f, cp); });
 }
 
 }  // namespace psh
