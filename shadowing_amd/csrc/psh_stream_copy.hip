@@ -65,9 +65,16 @@ namespace psh {
 #define PSH_COPY_QCAP 64              // deferred survivors a wave keeps (8-byte entries at the start of its fp32 tile)
 #define PSH_COPY_NAN 0x7e00u
 
-// a sample as the copy holds it: (f16)(y sc), round to nearest even; what is not a finite f16 is the quiet NaN
+// a sample as the copy holds it: (f16)(y sc), round to nearest even; what is not a finite f16 is the quiet NaN.
+// The compiler makes ONE instruction of the product and the conversion, a mixed-precision fma, and gives `(_Float16)(y * sc)`
+// the addend +0: -0 sc + 0 is +0, so a sample of -0 was stored as 0x0000 where the format says 0x8000
+// (tests/test_gpu_filter_copy_bytes.py).  The addend is therefore spelled out as -0, which keeps every product's value and
+// sign (sc is a power of two: the product is exact, the one rounding is the conversion's), and handed over through an empty
+// asm statement: a -0 the compiler can see is folded away and the +0 comes back.
 __device__ __forceinline__ unsigned short copy_encode(float y, float sc) {
-    const _Float16 h = (_Float16)(y * sc);
+    float nz = -0.0f;
+    asm("" : "+s"(nz));
+    const _Float16 h = (_Float16)__builtin_fmaf(y, sc, nz);
     const unsigned short b = __builtin_bit_cast(unsigned short, h);
     return (b & 0x7c00u) == 0x7c00u ? (unsigned short)PSH_COPY_NAN : b;
 }

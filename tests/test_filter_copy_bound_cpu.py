@@ -10,69 +10,16 @@ What is restated, rounding for rounding:
     the level   : stream_threshold_of with the copy route's constants PSH_COPY_A / PSH_COPY_B (read from psh_segment.h)
     per window  : reject iff t^ > thr (a NaN keeps the window)
 The property: NO window whose exact fp32 chain lies below the level is ever rejected.  The GPU side of it is
-tests/test_gpu_filter_copy.py (the admitted sets)."""
-import re
-from pathlib import Path
-
+tests/test_gpu_filter_copy.py (the admitted sets).  The five restated functions live in tests/_filter_copy.py: the device's
+bytes and step words are held to the very code this proof runs on (tests/test_gpu_filter_copy_bytes.py,
+tests/test_gpu_step_words.py)."""
 import numpy as np
 import pytest
 
 from _adversarial import KINDS, make as adversarial
+from _filter_copy import A_COPY, B_COPY, SEG, copy_exponent, encode, rejects, sexp_of, threshold
 
 f32, f16 = np.float32, np.float16
-SEG = 1024
-SRC = (Path(__file__).resolve().parent.parent / "shadowing_amd" / "csrc" / "psh_segment.h").read_text()
-
-
-def _const(name):
-    m = re.search(r"#define %s \(1\.0 / ([0-9.]+)\)" % name, SRC)
-    assert m, name
-    return 1.0 / float(m.group(1))
-
-
-A_COPY, B_COPY = _const("PSH_COPY_A"), _const("PSH_COPY_B")
-
-
-def copy_exponent(ds):
-    fin = ds[np.isfinite(ds)].astype(np.float64)
-    ms = float((fin * fin).sum() / fin.size) if fin.size else 0.0
-    if not (ms > 0.0 and ms < 1e300):
-        return 0
-    _, ex = np.frexp(np.sqrt(ms))
-    return int(np.clip(-int(ex), -60, 60))
-
-
-def encode(y, e_c):
-    with np.errstate(over="ignore", invalid="ignore"):
-        h = (y.astype(f32) * f32(2.0 ** e_c)).astype(f32).astype(f16)
-    h[~np.isfinite(h)] = f16(np.nan)
-    return h
-
-
-def sexp_of(x, tau):
-    """stream_sexp_of: None when the step is not armed."""
-    qbits = int(np.abs(x).max().view(np.uint32))
-    tbits = int(f32(tau).view(np.uint32))
-    if not (tau > 0 and np.isfinite(tau) and qbits < 0x7f800000):
-        return None
-    et = ((tbits >> 23) & 255) - 126
-    sexp = (12 - et) // 2 if 12 - et >= 0 else -((et - 12 + 1) // 2)
-    if qbits >= 0x00800000:
-        eq = ((qbits >> 23) & 255) - 126
-        sexp = min(sexp, 3 - eq)
-    if not (-60 <= sexp <= 60 and tbits >= 0x00800000):
-        return None
-    return sexp
-
-
-def threshold(x, W, tau, sc, a, b):
-    nxs = float(((x.astype(np.float64) * float(sc)) ** 2).sum())
-    bm = b * ((2 * W + 2) / 64.0 if W > 31 else 1.0)
-    T = float(tau) * float(sc) ** 2 * (1.0 + 1.0 / 131072.0) * (1.0 + 2.0 * a) - nxs * (1.0 - 3.0 * a) * (1.0 - 1e-12) + bm
-    Tf = f32(T)
-    if float(Tf) < T:
-        Tf = np.nextafter(Tf, f32(np.inf))
-    return Tf if np.isfinite(Tf) else None
 
 
 def exact_acc(yrow, x):
@@ -84,23 +31,6 @@ def exact_acc(yrow, x):
             D = (f32(x[j]) - yrow[j:j + n].astype(f32)).astype(f32).astype(np.float64)
             acc = (D * D + acc.astype(np.float64)).astype(f32)
     return acc
-
-
-def rejects(crow, x, W, s, e_c, thr):
-    """The reject mask of one segment's SEG windows from the copy's halves."""
-    delta = s - e_c
-    assert -14 <= delta <= 0
-    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
-        yh = (crow * f16(2.0 ** delta)).astype(f16)                  # numpy multiplies halves in float and rounds once
-        y2 = (yh * yh).astype(f16)
-        xh = (f32(-2.0) * (x.astype(f32) * f32(2.0 ** s)).astype(f32)).astype(f32).astype(f16)
-        n = len(crow) - W + 1
-        t = np.zeros(n, f32)
-        for j in range(W):                                            # fp32 accumulation of exact products, energies first
-            t = (t.astype(np.float64) + y2[j:j + n].astype(np.float64)).astype(f32)
-        for j in range(W):
-            t = (t.astype(np.float64) + yh[j:j + n].astype(np.float64) * float(xh[j])).astype(f32)
-        return t > thr                                                # (NaN > thr is False: kept)
 
 
 def run_case(kind, W, scale, qfac, seed, a=A_COPY, b=B_COPY, depth=200, stats=None):
