@@ -614,6 +614,33 @@ int psh_score_ensemble(int device, void* stream, const float* values, const doub
                        double* out_crps, double* out_pit_lo, double* out_pit_hi, double* out_mean, int32_t* out_status);
 
 /*
+ * The averaging weights of the k shadowing paths of every query, formed from their distances where they lie, for a grid of
+ * (eta, k') weightings in one call: what psh_weighted_moments, psh_weighted_quantiles, psh_score_ensemble and psh_hedged_mc
+ * take as given.  distances: device B x k float32.  etas (HOST, n_etas doubles) are the widths, ks (HOST, n_ks ints, each
+ * in 1 .. k; NULL with n_ks = 1: the one cut-off k) the cut-offs; set e = a * n_ks + c is (etas[a], ks[c]), and
+ * n_etas * n_ks <= PSH_SCORE_MAX_SETS.  out_weights: device (n_etas * n_ks) x B x k float64.  For one query and one set:
+ *   1. Order the paths by (distance ascending as numbers, path index ascending): -0.0 and +0.0 are equal, a NaN of either
+ *      sign comes after +inf, NaNs among themselves go by index (numpy's stable argsort).
+ *   2. The first k' paths are kept; every other path gets weight exactly 0.0.
+ *   3. With d_j converted to double and s = 2.0 * (eta * eta), computed once on the host in double:
+ *        z_j = -(d_j * d_j) / s      zmax = max of z over the kept paths (NaN if any kept z is NaN)
+ *        a_j = z_j - zmax            e_j = exp(a_j)      Z = sum of e_j over the kept paths, in a fixed order
+ *        w_j = e_j / Z
+ *      d_j * d_j is exact, so a_j is three IEEE operations and is bit-identical to the numpy twin's; the weights differ
+ *      from the twin's by exp (1 ulp a side), the order of the sum and the division: within (2 k' + 16) 2^-53 relative.
+ *   4. eta = +infinity is w_j = 1.0 / k' for the kept paths, whatever their distances.
+ *   5. A NaN among the kept distances makes every kept weight of that (e, b) NaN, and so do kept distances that are all
+ *      infinite; the consumers answer with their *_STATUS_WEIGHTS.  A NaN or inf past the cut-off is harmless.
+ *   6. No floating-point atomics: two calls give identical bits, and a set's bits do not depend on which other sets ride
+ *      the call.
+ * A NULL distances, etas or out_weights, B, k, n_etas or n_ks < 1, more than PSH_SCORE_MAX_SETS sets, an eta that is NaN or
+ * not > 0, a k' outside 1 .. k, or ks == NULL with n_ks != 1: PSH_ERR_ARG before anything touches the device; k > PSH_MAX_K:
+ * PSH_ERR_UNSUPPORTED.  The method heads shadowing_amd/csrc/psh_weights.hip; shadowing_amd/weights.py is its numpy twin.
+ */
+int psh_softmax_weights(int device, void* stream, const float* distances, int B, int k,
+                        const double* etas, int n_etas, const int* ks, int n_ks, double* out_weights);
+
+/*
  * Hedged Monte Carlo (Potters, Bouchaud, Sestovic 2001) on the k shadowing paths of each of B dates: the option prices,
  * Black-Scholes implied vols and strikes of a smile.  The method, in full, heads shadowing_amd/csrc/psh_hmc.hip (and
  * README "Option pricing"); shadowing_amd/pricing.py is its numpy twin.

@@ -7,6 +7,7 @@ library cannot be loaded, or a tensor is not on a HIP device, calls raise.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from pathlib import Path
 
 import torch
@@ -98,6 +99,7 @@ def _signatures() -> dict:
         "psh_weighted_moments": [i32, vp, vp, vp, i32, i32, i32, vp, vp],
         "psh_weighted_quantiles": [i32, vp, vp, vp, i32, i32, i32, P(f64), i32, vp, vp, vp, vp],
         "psh_score_ensemble": [i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
+        "psh_softmax_weights": [i32, vp, vp, i32, i32, P(f64), i32, P(i32), i32, vp],
         "psh_realized_variance": [i32, vp, vp, i64, i64, i32, P(i32), i32, i32, vp],
         "psh_hedged_mc": hedged_mc,
         "psh_hedged_mc_policy": hedged_mc + [vp],
@@ -1120,6 +1122,28 @@ def score_ensemble(values: torch.Tensor, weights: torch.Tensor | None, obs: torc
                                      crps.data_ptr(), pit_lo.data_ptr(), pit_hi.data_ptr(), mean.data_ptr(),
                                      status.data_ptr()), "psh_score_ensemble")
     return crps, pit_lo, pit_hi, mean, status
+
+
+def softmax_weights(distances: torch.Tensor, etas, ks=None) -> torch.Tensor:
+    """psh_softmax_weights on the (B, k) float32 distances of a scan, where they lie: the (len(etas) * len(ks), B, k) float64
+    weights of the grid, set a * len(ks) + c being (etas[a], ks[c]), on the device; nothing is synchronised here.  An eta of
+    None is the uniform weighting 1 / k'; ks=None is the one cut-off k."""
+    d = _dev_tensor(distances, torch.float32, "distances")
+    if d.dim() != 2 or d.numel() == 0:
+        raise ValueError(f"distances must be (B, k) and not empty, got {tuple(d.shape)}")
+    B, k = d.shape
+    es = [math.inf if eta is None else float(eta) for eta in etas]
+    kk = None if ks is None else [int(n) for n in ks]
+    n_ks = 1 if kk is None else len(kk)
+    if not es or n_ks < 1 or len(es) * n_ks > PSH_SCORE_MAX_SETS:
+        raise ValueError(f"{len(es)} etas x {n_ks} ks weight sets: 1 to {PSH_SCORE_MAX_SETS} a call")
+    if k > PSH_MAX_K:
+        raise NativeLibraryError(f"psh_softmax_weights takes k <= {PSH_MAX_K} paths, got {k}")
+    out = torch.empty((len(es) * n_ks, B, k), dtype=torch.float64, device=d.device)
+    _check(load().psh_softmax_weights(d.device.index, _stream_ptr(d.device), d.data_ptr(), B, k, (C.c_double * len(es))(*es),
+                                      len(es), None if kk is None else (C.c_int * n_ks)(*kk), n_ks, out.data_ptr()),
+           "psh_softmax_weights")
+    return out
 
 
 def _uniform_rows(x: torch.Tensor):

@@ -1527,6 +1527,28 @@ int psh_score_ensemble(int device, void* stream, const float* values, const doub
     return PSH_OK;
 }
 
+int psh_softmax_weights(int device, void* stream, const float* distances, int B, int k, const double* etas, int n_etas,
+                        const int* ks, int n_ks, double* out_weights) {
+    if (!distances || !etas || !out_weights || B <= 0 || k <= 0 || n_etas <= 0 || n_ks <= 0 ||
+        (int64_t)n_etas * n_ks > PSH_SCORE_MAX_SETS)
+        return PSH_ERR_ARG;
+    WeightsArgs a{};
+    for (int i = 0; i < n_etas; ++i) {
+        if (!(etas[i] > 0.0)) return PSH_ERR_ARG;                           // (NaN fails it too)
+        a.s[i] = 2.0 * (etas[i] * etas[i]);                                 // +infinity stays +infinity: uniform weights
+    }
+    for (int i = 0; i < n_ks; ++i) {
+        const int kc = ks ? ks[i] : k;
+        if (kc < 1 || kc > k || (!ks && n_ks != 1)) return PSH_ERR_ARG;
+        a.ks[i] = kc;
+    }
+    if (k > PSH_MAX_K) return PSH_ERR_UNSUPPORTED;                          // (one workgroup per row)
+    a.distances = distances; a.B = B; a.k = k; a.n_etas = n_etas; a.n_ks = n_ks; a.out = out_weights;
+    GUARD_DEVICE(device);
+    HIP_TRY(launch_softmax_weights(a, (hipStream_t)stream));
+    return PSH_OK;
+}
+
 // what every hedged Monte Carlo entry point asks of the paths, the grid of maturities and strikes and the regression
 static int hmc_check_sizes(const float* dlnx, int64_t row_stride, int B, int k, int len, double x_init, double rate, const int* Ts,
                            int nT, const double* Ms, int nM, int degree, int kind) {

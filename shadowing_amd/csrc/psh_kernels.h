@@ -431,6 +431,17 @@ struct ScoreArgs {
 };
 hipError_t launch_score(const ScoreArgs& a, hipStream_t s);
 
+// psh_weights.hip: the averaging weights of the k paths from their distances, for every (eta, k') of a grid (psh_softmax_weights)
+struct WeightsArgs {
+    const float* distances;   // (B, k)
+    int B, k, n_etas, n_ks;   // set e = a * n_ks + c is (s[a], ks[c]); n_etas * n_ks <= PSH_SCORE_MAX_SETS
+    int sets_per_group;       // set by the launcher: the sets one workgroup serves
+    double s[64];             // 2 eta^2 of every width, +infinity: uniform weights
+    int ks[64];               // the cut-offs, each in 1 .. k
+    double* out;              // (n_etas * n_ks, B, k)
+};
+hipError_t launch_softmax_weights(const WeightsArgs& a, hipStream_t s);
+
 // psh_hmc.hip: hedged Monte Carlo on the shadowing paths of a date (psh_hedged_mc)
 #define PSH_HMC_SG 3              // strikes a block solves (the Gram matrix of a step is shared by them)
 #define PSH_HMC_MAX_T 64

@@ -1,5 +1,6 @@
 // psh_sort_lds.h -- the in-LDS sort and the fixed-order scan that the kernels over the k shadowing paths of a column share:
-// psh_quantiles.hip (psh_weighted_quantiles) and psh_scoring.hip (psh_score_ensemble).  Path j of a column is the 64-bit
+// psh_quantiles.hip (psh_weighted_quantiles), psh_scoring.hip (psh_score_ensemble) and psh_weights.hip (psh_softmax_weights,
+// on the k distances of a query row, a NaN taking the largest key first).  Path j of a column is the 64-bit
 // entry (order-preserving 32-bit key of its float32 value) << 32 | j, -0.0 taking +0.0's key, so entries are unique and
 // ties break by path index; the bitonic network runs NB index bits a pass on registers, and entry i lies at i + i / 16 in
 // LDS.  The method and the bank arithmetic head psh_quantiles.hip.

@@ -146,6 +146,7 @@ class PathShadowing:
         self.last_predict_reduction = None   # device_predict: "device" (psh_weighted_moments) / "host" (the class's own avg / std)
         self.last_quantile_reduction = None  # predict_quantiles: "device" (psh_weighted_quantiles) / "host" (the numpy twin)
         self.last_score_reduction = None     # score: "device" (psh_score_ensemble) / "host" (the numpy twin)
+        self.last_weights = None             # predict, predict_quantiles, score, smile: "device" (psh_softmax_weights) / "host"
 
     @staticmethod
     def _load_with_scatspectra(dataset):
@@ -538,7 +539,7 @@ class PathShadowing:
                 self._workspace.arm()
             out = self._native_scan(x, y, k)
         kept, down = consume(*out)
-        return kept, self._to_host(*down)
+        return kept, (self._to_host(*down) if down else ())
 
     def _shadow_prepared(self, x: torch.Tensor, y: torch.Tensor, k: int):
         """shadow() for ONE Identity query as one blocking library call (_native.BlockingShadow -> psh_shadow_blocking: the fused
@@ -731,10 +732,13 @@ class PathShadowing:
         values = to_predict(future)
         return proba.avg(values, axis=1), proba.std(values, axis=1)
 
-    def _scan_and_evaluate(self, x: torch.Tensor, y: torch.Tensor, k: int, to_predict: Callable):
+    def _scan_and_evaluate(self, x: torch.Tensor, y: torch.Tensor, k: int, to_predict: Callable, reduce: Callable | None = None):
         """The prologue of every device-side prediction: the native scan, the path gather and `to_predict` on the device
-        tensor of the out-context.  Returns (values (B, k, ...) on the device, distances (B, k) on the host): the paths
-        never leave HBM."""
+        tensor of the out-context; the paths never leave HBM.  Returns (values (B, k, ...) on the device, what came down as
+        numpy arrays, whether `reduce` took the call).  What comes down is the (B, k) distances -- or, with device_weights,
+        the rest of the flow enqueued behind the statistic: `reduce(values, d)` sees it and the scan's own distances on the
+        device, enqueues the weights and the reduction and returns the device results to bring down IN PLACE of the
+        distances, or None to decline."""
         length = x.shape[-1] + self.context.get_out_times()
 
         def evaluate(d, idx, ds):
@@ -744,13 +748,30 @@ class PathShadowing:
                 raise TypeError("device_predict: to_predict must map the (B, k, C, h) torch tensor of out-context paths to a "
                                 f"torch tensor (B, k, ...); got {type(values).__name__}"
                                 f"{tuple(getattr(values, 'shape', ()))}")
-            return values, (d,)
+            down = reduce(values, d) if reduce is not None else None
+            return (values, down is not None), ((d,) if down is None else tuple(down))
 
-        values, (d_host,) = self._scan_then(x, y, k, evaluate)
-        return values, d_host
+        (values, reduced), host = self._scan_then(x, y, k, evaluate)
+        return values, host, reduced
+
+    def _device_eta(self, proba_name: str, eta: float | None, moments: bool = False) -> float | None:
+        """The width psh_softmax_weights takes for this averaging (None: 1 / k'), once the INSTALLED class has shown on a
+        probe that its weights are the formula the kernel restates (weights_follow_twin) -- and, with `moments`, that its
+        avg / std are the weighted moments of those weights (moment_weights).  TypeError otherwise: device_weights=True
+        does not fall back silently."""
+        probe = _WEIGHT_PROBE.astype(np.float64)
+        for pe in (0.07, None):
+            proba = self.init_averaging_proba(proba_name, probe, pe)
+            if not weights_follow_twin(proba, _WEIGHT_PROBE, None if proba_name == "uniform" else pe):
+                raise TypeError(f"device_weights=True: the weights of the installed {type(proba).__name__} are not the ones "
+                                "psh_softmax_weights forms (or it exposes none); use device_weights=False")
+            if moments and moment_weights(proba, *probe.shape) is None:
+                raise TypeError(f"device_weights=True: avg / std of the installed {type(proba).__name__} are not the weighted "
+                                "moments of its weights; use device_weights=False")
+        return None if proba_name == "uniform" else eta
 
     def _predict_on_device(self, x: torch.Tensor, y: torch.Tensor, k: int, to_predict: Callable,
-                           proba_name: str, eta: float | None):
+                           proba_name: str, eta: float | None, device_weights: bool = False):
         """shadow() + predict_from_paths() with the PATHS kept on the GPU: the k paths of every query (74 MB for
         the tutorial's call) stay in HBM and `to_predict` is evaluated there on the device tensor of their
         out-context; what crosses PCIe are the (B, k) distances -- the installed DiscreteProba turns them into its weights
@@ -759,8 +780,23 @@ class PathShadowing:
         (ref :251-252) are reduced on the device by psh_weighted_moments when the class's own avg / std are the weighted
         moments of weights it exposes (moment_weights checks that on a probe; `last_predict_reduction` says which way a
         call went); any other class receives the (B, k, ...) statistic on the host and reduces it itself.  Only called
-        when the caller opted in (see predict())."""
-        values, d_host = self._scan_and_evaluate(x, y, k, to_predict)
+        when the caller opted in (see predict()).  device_weights=True: the weights are formed on the scan's own device
+        distances (psh_softmax_weights) and reduced behind it; only the moments come down, in one synchronisation."""
+        reduce = None
+        if device_weights:
+            eta_dev = self._device_eta(proba_name, eta, moments=True)
+
+            def reduce(values, d):
+                if not (values.is_cuda and values.dtype == torch.float32):
+                    return None
+                return _native.weighted_moments(values.contiguous(), _native.softmax_weights(d, [eta_dev])[0])
+
+        values, host, reduced = self._scan_and_evaluate(x, y, k, to_predict, reduce)
+        self.last_weights = "device" if reduced else "host"
+        if reduced:
+            self.last_predict_reduction = "device"
+            return host
+        d_host = host[0]
         # what has crossed PCIe so far: the (B, k) distances.  The installed class turns them into weights on the host (its
         # formula is its own); if its avg / std ARE the weighted moments of those weights -- checked on a probe, the class
         # stays authoritative -- the (B, k, ...) statistic is reduced where it is (psh_weighted_moments) and only the
@@ -779,23 +815,29 @@ class PathShadowing:
 
     def predict(self, x_context: ArrayType, k: int, to_predict: Callable, eta: float | None = None,
                 proba_name: str = "softmax", n_dataset_splits: int = 1, n_context_splits: int = 1,
-                cuda: bool = False, device_predict: bool | None = None) -> tuple[np.ndarray, np.ndarray]:
+                cuda: bool = False, device_predict: bool | None = None, device_weights: bool = False
+                ) -> tuple[np.ndarray, np.ndarray]:
         """shadow() + predict_from_paths() over `n_context_splits` batches of queries (ref :256-301).
 
         `to_predict` receives what the reference hands it: the numpy array of out-context paths.  OPT-IN, with
         cuda=True on a natively scanned configuration: `device_predict=True` -- or a callable that declares
         `to_predict.accepts_torch = True`, as `shadowing.realized_variance` does -- evaluates `to_predict` on the
         device tensor instead, so the paths never leave HBM (_predict_on_device).  A numpy-style callable is NOT
-        silently given tensors: `x.std(-1)` is Bessel-corrected in torch and not in numpy."""
+        silently given tensors: `x.std(-1)` is Bessel-corrected in torch and not in numpy.  device_weights=True (on the
+        device route with k <= PSH_MAX_K; ignored elsewhere): the weights are formed on the device too (README "Forming the
+        weights on the device"; `last_weights` says "device" or "host")."""
         if device_predict is None:
             device_predict = bool(getattr(to_predict, "accepts_torch", False))
+        device_weights = bool(device_weights) and k <= _native.PSH_MAX_K
 
         def on_host(xr):
             d, paths, _ = self.shadow(xr, k, n_dataset_splits, cuda)
+            self.last_weights = "host"
             return self.predict_from_paths(d, paths, to_predict, proba_name, eta)
 
         parts = self._over_context_splits(x_context, k, n_context_splits, cuda, device_predict, on_host,
-                                          lambda xr, y: self._predict_on_device(xr, y, k, to_predict, proba_name, eta), tqdm)
+                                          lambda xr, y: self._predict_on_device(xr, y, k, to_predict, proba_name, eta,
+                                                                                device_weights), tqdm)
         return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
 
     def _over_context_splits(self, x_context: ArrayType, k: int, n_context_splits: int, cuda: bool, device_wanted: bool,
@@ -842,23 +884,38 @@ class PathShadowing:
 
     def predict_quantiles(self, x_context: ArrayType, k: int, to_predict: Callable, levels, eta: float | None = None,
                           proba_name: str = "softmax", n_dataset_splits: int = 1, n_context_splits: int = 1,
-                          cuda: bool = False, device_predict: bool | None = None):
+                          cuda: bool = False, device_predict: bool | None = None, device_weights: bool = False):
         """shadow() + quantiles_from_paths() over `n_context_splits` batches of queries: predict()'s twin for the quantiles
         and tail means of the conditional distribution, with the same opt-in rule for `device_predict`.  With cuda=True,
         device_predict=True on a natively scanned configuration the paths and the statistic stay in HBM: the (B, k)
         distances come down, the weights go up, and only the three (B, Q, ...) results come back
-        (`last_quantile_reduction` says "device" or "host")."""
-        from .quantiles import PredictiveQuantiles, weighted_quantiles
+        (`last_quantile_reduction` says "device" or "host").  device_weights=True on that route: no distances come down
+        and no weights go up -- psh_softmax_weights forms them behind the scan (`last_weights`)."""
+        from .quantiles import PredictiveQuantiles, _check_levels, weighted_quantiles
         if device_predict is None:
             device_predict = bool(getattr(to_predict, "accepts_torch", False))
 
         def on_host(xr):
             d, paths, _ = self.shadow(xr, k, n_dataset_splits, cuda)
-            self.last_quantile_reduction = "host"
+            self.last_quantile_reduction = self.last_weights = "host"
             return self.quantiles_from_paths(d, paths, to_predict, levels, proba_name, eta)
 
         def on_device(xr, y):
-            values, d_host = self._scan_and_evaluate(xr, y, k, to_predict)
+            reduce = None
+            if device_weights:
+                lv, eta_dev = _check_levels(levels), self._device_eta(proba_name, eta)
+
+                def reduce(values, d):
+                    if not (values.is_cuda and values.dtype == torch.float32):
+                        return None
+                    return _native.weighted_quantiles(values.contiguous(), _native.softmax_weights(d, [eta_dev])[0], lv)
+
+            values, host, reduced = self._scan_and_evaluate(xr, y, k, to_predict, reduce)
+            self.last_weights = "device" if reduced else "host"
+            if reduced:
+                self.last_quantile_reduction = "device"
+                return PredictiveQuantiles(lv, *host)
+            d_host = host[0]
             w = self._quantile_weights(proba_name, d_host, eta)
             on_dev = values.is_cuda and values.dtype == torch.float32
             self.last_quantile_reduction = "device" if on_dev else "host"
@@ -874,17 +931,9 @@ class PathShadowing:
         """The (len(etas) * len(ks), B, k) float64 weight sets of a grid: set (eta, k') holds the installed averaging class's
         own weights for the k' smallest distances of each query (stable argsort; shadow() returns them ascending) and 0 for
         the other k - k' paths.  Returns (weights, etas, ks)."""
-        from .scoring import MAX_SETS
         d = np.asarray(distances, dtype=np.float64)
         B, k = d.shape
-        etas = tuple(etas)
-        ks = (k,) if ks is None else tuple(int(n) for n in ks)
-        if not etas or not ks:
-            raise ValueError("score: etas and ks must not be empty")
-        if len(etas) * len(ks) > MAX_SETS:
-            raise ValueError(f"score: {len(etas)} etas x {len(ks)} ks = {len(etas) * len(ks)} weight sets, at most {MAX_SETS} a call")
-        if min(ks) < 1 or max(ks) > k:
-            raise ValueError(f"score: every k' must lie in 1 .. k = {k}, got {list(ks)}")
+        etas, ks = self._score_grid(k, etas, ks)
         order = np.argsort(d, axis=1, kind="stable")
         w = np.zeros((len(etas), len(ks), B, k))
         for a, eta in enumerate(etas):
@@ -893,6 +942,20 @@ class PathShadowing:
                 wk = averaging_weights(self.init_averaging_proba(proba_name, np.take_along_axis(d, near, axis=1), eta), B, kc)
                 np.put_along_axis(w[a, c], near, 1.0 if wk is None else wk, axis=1)
         return w.reshape(len(etas) * len(ks), B, k), etas, ks
+
+    @staticmethod
+    def _score_grid(k: int, etas, ks):
+        """The grid of a score() call as tuples (ks=None: the one cut-off k), checked."""
+        from .scoring import MAX_SETS
+        etas = tuple(etas)
+        ks = (k,) if ks is None else tuple(int(n) for n in ks)
+        if not etas or not ks:
+            raise ValueError("score: etas and ks must not be empty")
+        if len(etas) * len(ks) > MAX_SETS:
+            raise ValueError(f"score: {len(etas)} etas x {len(ks)} ks = {len(etas) * len(ks)} weight sets, at most {MAX_SETS} a call")
+        if min(ks) < 1 or max(ks) > k:
+            raise ValueError(f"score: every k' must lie in 1 .. k = {k}, got {list(ks)}")
+        return etas, ks
 
     def _observe(self, x_realized, to_predict: Callable, device=None):
         """The realised statistic (B, ...): `to_predict` sees the realised out-context (B, C, h) as it sees the paths', one
@@ -924,11 +987,13 @@ class PathShadowing:
 
     def score(self, x_context: ArrayType, x_realized: ArrayType, k: int, to_predict: Callable, etas, ks=None,
               proba_name: str = "softmax", n_dataset_splits: int = 1, n_context_splits: int = 1,
-              cuda: bool = False, device_predict: bool | None = None):
+              cuda: bool = False, device_predict: bool | None = None, device_weights: bool = False):
         """shadow() + score_from_paths() over `n_context_splits` batches of queries, with predict()'s opt-in rule for
         `device_predict`.  With cuda=True, device_predict=True on a natively scanned configuration with k <= PSH_MAX_K the
         scan runs once, the paths and the statistic stay in HBM: the (B, k) distances come down, the (E, B, k) weights of
-        the grid go up, and only the four (E, B, ...) results come back (`last_score_reduction` says "device" or "host")."""
+        the grid go up, and only the four (E, B, ...) results come back (`last_score_reduction` says "device" or "host").
+        device_weights=True on that route: the (E, B, k) weights are formed where the distances lie (psh_softmax_weights)
+        and scored behind the scan; nothing but the results crosses PCIe, in one synchronisation (`last_weights`)."""
         from .scoring import EnsembleScore, score_ensemble
         if device_predict is None:
             device_predict = bool(getattr(to_predict, "accepts_torch", False))
@@ -940,15 +1005,32 @@ class PathShadowing:
 
         def on_host(xr):
             d, paths, _ = self.shadow(xr, k, n_dataset_splits, cuda)
-            self.last_score_reduction = "host"
+            self.last_score_reduction = self.last_weights = "host"
             return self.score_from_paths(d, paths, _numpy(next(batches)), to_predict, etas, ks, proba_name)
 
         def on_device(xr, y):
-            values, d_host = self._scan_and_evaluate(xr, y, k, to_predict)
+            realized = next(batches)
+            reduce = None
+            if device_weights:
+                es, kk = self._score_grid(k, etas, ks)
+                etas_dev = [self._device_eta(proba_name, eta) for eta in es]
+
+                def reduce(values, d):
+                    if not (values.is_cuda and values.dtype == torch.float32):
+                        return None
+                    obs = self._observe(realized, to_predict, values.device).to(torch.float32).contiguous()
+                    return _native.score_ensemble(values.contiguous(), _native.softmax_weights(d, etas_dev, kk), obs)
+
+            values, host, reduced = self._scan_and_evaluate(xr, y, k, to_predict, reduce)
+            self.last_weights = "device" if reduced else "host"
+            if reduced:
+                self.last_score_reduction = "device"
+                return self._grid_score(EnsembleScore(*host), es, kk)
+            d_host = host[0]
             w, es, kk = self._score_weights(proba_name, d_host, etas, ks)
             on_dev = values.is_cuda and values.dtype == torch.float32
             self.last_score_reduction = "device" if on_dev else "host"
-            obs = self._observe(next(batches), to_predict, values.device)
+            obs = self._observe(realized, to_predict, values.device)
             return self._grid_score(score_ensemble(values, w, obs, cuda=on_dev), es, kk)
 
         parts = self._over_context_splits(x_context, k, n_context_splits, cuda, device_predict and k <= _native.PSH_MAX_K,
@@ -980,25 +1062,41 @@ class PathShadowing:
 
     def smile(self, x_context: ArrayType, k: int, Ts, Ms, eta: float | None = None, proba_name: str = "softmax",
               r: float = 0.0, x_init: float = 100.0, channel: int = 0, degree: int = 3, kind: str = "otm",
-              n_dataset_splits: int = 1, n_context_splits: int = 1, cuda: bool = False, report: bool = False):
+              n_dataset_splits: int = 1, n_context_splits: int = 1, cuda: bool = False, report: bool = False,
+              device_weights: bool = False):
         """shadow() + smile_from_paths() over `n_context_splits` batches of queries.  With cuda=True on a natively scanned
         configuration the gathered paths stay in HBM: the (B, k) distances come to the host for the averaging class's
         weights, the weights go back up, psh_hedged_mc prices on the out-context view of the paths, and only the
         (B, nT, nM) results come down.  Anything else (k > PSH_MAX_K included) prices the host results of shadow().
         report=True: the fit keeps its policy and psh_hedge_replay replays it on the same view -- the paths and the policy
-        (Smile.policy.coef, a HIP tensor) stay in HBM, the (B, nT, nM) report fields come down."""
+        (Smile.policy.coef, a HIP tensor) stay in HBM, the (B, nT, nM) report fields come down.  device_weights=True on
+        that route: psh_softmax_weights forms the weights on the scan's device distances; neither crosses PCIe
+        (`last_weights`)."""
         from .pricing import concat_smiles, smile_from_log_returns
         if not isinstance(self.context, PredictionContext):
             raise NotImplementedError("smile: only a PredictionContext has an out-context to price on")
 
         def on_host(xr):
             d, paths, _ = self.shadow(xr, k, n_dataset_splits, cuda)
+            self.last_weights = "host"
             return self.smile_from_paths(d, paths, Ts, Ms, proba_name, eta, r, x_init, channel, degree, kind, report)
 
         def on_device(xr, y):
-            future, d_host = self._scan_and_evaluate(xr, y, k, lambda out_context: out_context[:, :, channel, :])
-            w = self._smile_weights(proba_name, d_host, eta)
-            wt = None if w is None else torch.from_numpy(w.copy()).to(future.device)
+            reduce, held = None, {}
+            if device_weights:
+                eta_dev = self._device_eta(proba_name, eta)
+
+                def reduce(future, d):
+                    held["w"] = _native.softmax_weights(d, [eta_dev])[0]
+                    return ()                                         # (the pricing brings its own results down)
+
+            future, host, reduced = self._scan_and_evaluate(xr, y, k, lambda out_context: out_context[:, :, channel, :], reduce)
+            self.last_weights = "device" if reduced else "host"
+            if reduced:
+                wt = held["w"]
+            else:
+                w = self._smile_weights(proba_name, host[0], eta)
+                wt = None if w is None else torch.from_numpy(w.copy()).to(future.device)
             return smile_from_log_returns(future, wt, Ts, Ms, x_init, r, degree=degree, kind=kind, cuda=True, report=report)
 
         return concat_smiles(self._over_context_splits(x_context, k, n_context_splits, cuda, k <= _native.PSH_MAX_K,
@@ -1046,6 +1144,30 @@ def averaging_weights(proba, B: int, k: int):
     while w.ndim > 2 and w.shape[-1] == 1:
         w = w[..., 0]
     return np.ascontiguousarray(np.broadcast_to(w, (B, k)))
+
+
+_WEIGHT_CLASSES: dict = {}      # (averaging class, eta is None) -> its `weights` ARE the ones psh_softmax_weights forms (probed once)
+_WEIGHT_PROBE = np.array([[0.0, 0.011, 0.02, 0.02, 0.05, 0.3], [0.004, 0.004, 0.09, 0.1, 0.11, 0.9]], dtype=np.float32)
+
+
+def weights_follow_twin(proba, distances: np.ndarray, eta: float | None) -> bool:
+    """Whether the `weights` of an averaging object built on `distances` (B, k) with `eta` are the ones the twin of
+    psh_softmax_weights gives for them (weights.softmax_weights, rtol 1e-10): the device may restate the formula of such a
+    class, and of no other.  An object that exposes no weights, or other ones (an installed scatspectra with another
+    formula), is False.  The comparison runs once per averaging CLASS and kind of eta."""
+    key = (type(proba), eta is None)
+    verdict = _WEIGHT_CLASSES.get(key)
+    if verdict is None:
+        from .weights import softmax_weights
+        d = np.asarray(distances, dtype=np.float32)
+        try:
+            w = averaging_weights(proba, *d.shape)
+            w = np.full(d.shape, 1.0 / d.shape[1]) if w is None else w
+            verdict = bool(np.allclose(w, softmax_weights(d, [eta], cuda=False)[0, 0], rtol=1e-10, atol=1e-300))
+        except Exception:  # noqa: BLE001
+            verdict = False
+        _WEIGHT_CLASSES[key] = verdict
+    return verdict
 
 
 _MOMENT_CLASSES: dict = {}      # averaging class -> its avg / std ARE the weighted moments of its `weights` (probed once)
