@@ -668,6 +668,54 @@ int psh_hedged_mc(int device, void* stream, const float* dlnx, int64_t row_strid
                   int32_t* out_status);
 
 /*
+ * The weights of the k shadowing paths of each of B dates, calibrated to quoted vanillas: the weighted Monte Carlo of
+ * Avellaneda, Buff, Friedman, Grandchamp, Kruk and Newman (2001).  The weights move as little as possible in relative
+ * entropy from the prior until the weighted paths reprice the quotes; the result is a (B, k) float64 array that
+ * psh_hedged_mc, psh_hedge_replay, psh_weighted_quantiles, psh_weighted_moments and psh_score_ensemble take as given.  The
+ * method heads shadowing_amd/csrc/psh_calibrate.hip (and README "Calibrating to market quotes"); shadowing_amd/calibration.py
+ * (calibrate_host) is its numpy twin.
+ *   dlnx, row_stride, B, k, len: as psh_hedged_mc;  prior: device B x k float64 prior weights p_i >= 0, or NULL: 1;
+ *   Ts: HOST array of nT maturities in samples, 1 <= T <= len;  strike, target: device B x nT x nM float64, the quoted
+ *   strikes and prices; a NaN target: not quoted;  kind: PSH_HMC_OTM (a call iff K >= x_init exp(rho T)) / CALL / PUT;
+ *   martingale != 0: each maturity adds the instrument "forward", payoff S_T, target x_init exp(rho T) undiscounted.
+ * For one date, all in double, rho = rate / 252:
+ *     l_0 = 0, l_{n+1} = l_n + r[i, n]  (sequential)      S_{T,i} = x_init exp(l_T)
+ *     g_ij = exp(-rho T_j) payoff_j(S_{T_j, i})           forward: g = exp(-rho T) S_T, c = x_init
+ *     h_ij = (g_ij - c_j) / x_init                        instrument j = q * nM + m;  forwards: nT * nM + q
+ *     J = nT * nM + (martingale ? nT : 0) <= PSH_CAL_MAX_INSTRUMENTS       (beyond: PSH_ERR_UNSUPPORTED)
+ *     a_i = sum_j lambda_j h_ij     amax = max of a over p_i > 0     e_i = p_i exp(a_i - amax)     Z = sum e_i (fixed order)
+ *     q_i = e_i / Z                 P = sum p_i
+ *   lambda minimises Phi = amax + ln(Z / P) + (eps / 2) |lambda|^2, eps >= 0 (0: the hard constraint; > 0 always has a
+ *   solution, which reprices quote j with error -eps lambda_j x_init):
+ *     grad_j = mu_j + eps lambda_j,  mu_j = sum_i q_i h_ij,   H_jl = sum_i q_i h_ij h_il - mu_j mu_l + eps delta_jl
+ *   by Newton steps from lambda = 0: success when max_j |grad_j| <= tol; else H d = -grad by Cholesky in instrument order
+ *   (an unknown whose diagonal is not > 0 or whose pivot is <= 1e-10 of it is dropped: step 0; an unquoted instrument is
+ *   never an unknown), t = 1, 1/2, ..., 2^-40 until Phi(lambda + t d) <= Phi(lambda) + 1e-4 t grad.d, at most max_iter
+ *   steps.  Every unknown dropped above tol, a failed line search, or max_iter steps: the last iterate, NOT_CONVERGED.
+ *   out_weights: device B x k (q; exactly 0 where p_i = 0);  out_lambda: B x J (0 for unquoted and dropped unknowns);
+ *   out_model: B x J, sum_i q_i g_ij of every instrument;  out_info: B x 4 = [kl = sum q_i (a_i - amax) - ln(Z / P),
+ *   n_eff = 1 / sum q_i^2, Newton steps taken, max_j |grad_j| at the end];  out_status: B int32, PSH_CAL_STATUS_* bits.
+ *   workspace: device, psh_calibrate_workspace_bytes(B, k, nT) bytes (PSH_ERR_WORKSPACE when smaller).
+ * A path with p_i = 0 contributes nothing whatever its returns; scaling the prior by a power of two changes no bit; no
+ * floating-point atomics: two calls give identical bits, and a date's bits do not depend on the other dates of the call.
+ * A NULL pointer (prior apart), a size < 1, row_stride < len, eps negative or NaN, tol not > 0, max_iter < 0, a T outside
+ * 1 .. len: PSH_ERR_ARG before anything touches the device; k > PSH_MAX_K or J > PSH_CAL_MAX_INSTRUMENTS: PSH_ERR_UNSUPPORTED.
+ */
+#define PSH_CAL_MAX_INSTRUMENTS 32
+#define PSH_CAL_STATUS_OK            0
+#define PSH_CAL_STATUS_NONFINITE     1   /* a path with p_i > 0 has a non-finite return in [0, max Ts): all outputs NaN */
+#define PSH_CAL_STATUS_WEIGHTS       2   /* a prior weight negative or not finite, or their sum not > 0: all outputs NaN */
+#define PSH_CAL_STATUS_QUOTES        4   /* a strike not finite and > 0, or an infinite target: all outputs NaN */
+#define PSH_CAL_STATUS_NOT_CONVERGED 8   /* the outputs are the last iterate */
+#define PSH_CAL_STATUS_DROPPED       16  /* an unknown was dropped in the last solve (redundant quotes): informational */
+int psh_calibrate_workspace_bytes(int B, int k, int nT, size_t* out);
+int psh_calibrate_weights(int device, void* stream, const float* dlnx, int64_t row_stride, int B, int k, int len,
+                          const double* prior, double x_init, double rate, const int* Ts, int nT, const double* strike,
+                          const double* target, int nM, int kind, int martingale, double eps, double tol, int max_iter,
+                          double* out_weights, double* out_lambda, double* out_model, double* out_info, int32_t* out_status,
+                          void* workspace, size_t workspace_bytes);
+
+/*
  * The hedge of a smile: the fit of psh_hedged_mc with its policy kept, and the replay of a policy on paths.  The
  * definition, in full, heads shadowing_amd/csrc/psh_hmc_report.hip (and README "Option pricing"); pricing.py
  * (replay_host) is the numpy twin.

@@ -101,6 +101,9 @@ def _signatures() -> dict:
         "psh_score_ensemble": [i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
         "psh_softmax_weights": [i32, vp, vp, i32, i32, P(f64), i32, P(i32), i32, vp],
         "psh_realized_variance": [i32, vp, vp, i64, i64, i32, P(i32), i32, i32, vp],
+        "psh_calibrate_workspace_bytes": [i32, i32, i32, P(sz)],
+        "psh_calibrate_weights": [i32, vp, vp, i64, i32, i32, i32, vp, f64, f64, P(i32), i32, vp, vp, i32, i32, i32, f64, f64, i32,
+                                  vp, vp, vp, vp, vp, vp, sz],
         "psh_hedged_mc": hedged_mc,
         "psh_hedged_mc_policy": hedged_mc + [vp],
         "psh_hmc_policy_doubles": [i32, i32, i32, i32, i32, P(sz)],
@@ -1363,6 +1366,39 @@ def hedge_replay(dlnx: torch.Tensor, weights: torch.Tensor | None, Ts, Ms, polic
     ws = _workspace(load().psh_hedge_replay_workspace_bytes, B, k, nT, nM, device=x.device)
     _check(load().psh_hedge_replay(*head, pol.data_ptr(), ks.data_ptr(), ce.data_ptr(), out["sums"].data_ptr(), _ptr(out.get("pnl")),
                                    out["status"].data_ptr(), ws.data_ptr(), ws.numel() * 8), "psh_hedge_replay")
+    return out
+
+
+PSH_CAL_MAX_INSTRUMENTS = 32
+
+
+def calibrate_weights(dlnx: torch.Tensor, prior: torch.Tensor | None, Ts, strike: torch.Tensor, target: torch.Tensor,
+                      x_init: float = 100.0, rate: float = 0.0, kind: int = PSH_HMC_OTM, martingale: bool = True,
+                      eps: float = 1e-6, tol: float = 1e-8, max_iter: int = 100) -> dict:
+    """psh_calibrate_weights on float32 log-returns (B, k, L) (as hedged_mc's: any constant row stride), (B, k) float64 prior
+    weights or None, and (B, nT, nM) float64 device strikes and quoted prices (NaN: not quoted).  Returns device tensors:
+    weights (B, k), lam and model (B, J), info (B, 4) = [kl, n_eff, steps, max |grad|] float64, status (B,) int32; nothing
+    is synchronised here."""
+    x, Ts, _, head = _hmc_inputs(dlnx, prior, Ts, [0.0], x_init, rate, 1, kind)
+    (B, k), nT = x.shape[:2], len(Ts)
+    K = _dev_tensor(strike, torch.float64, "strike")
+    c = _dev_tensor(target, torch.float64, "target")
+    if K.dim() != 3 or tuple(K.shape[:2]) != (B, nT) or K.shape[2] < 1 or c.shape != K.shape:
+        raise ValueError(f"strike and target must be (B, nT, nM) = ({B}, {nT}, nM), got {tuple(K.shape)} and {tuple(c.shape)}")
+    if K.device != x.device or c.device != x.device:
+        raise ValueError("strike, target and dlnx must be on the same device")
+    nM = K.shape[2]
+    J = nT * nM + (nT if martingale else 0)
+    if k > PSH_MAX_K or J > PSH_CAL_MAX_INSTRUMENTS:
+        raise NativeLibraryError(f"psh_calibrate_weights takes k <= {PSH_MAX_K} paths and at most {PSH_CAL_MAX_INSTRUMENTS} "
+                                 f"instruments, got k = {k}, J = {J}")
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=x.device)   # noqa: E731
+    out = {"weights": f64(B, k), "lam": f64(B, J), "model": f64(B, J), "info": f64(B, 4),
+           "status": torch.empty((B,), dtype=torch.int32, device=x.device)}
+    ws = _workspace(load().psh_calibrate_workspace_bytes, B, k, max(nT, 1), device=x.device)
+    _check(load().psh_calibrate_weights(*head[:12], K.data_ptr(), c.data_ptr(), nM, int(kind), int(bool(martingale)), float(eps),
+                                        float(tol), int(max_iter), *(out[n].data_ptr() for n in ("weights", "lam", "model", "info", "status")),
+                                        ws.data_ptr(), ws.numel() * 8), "psh_calibrate_weights")
     return out
 
 

@@ -1549,6 +1549,50 @@ int psh_softmax_weights(int device, void* stream, const float* distances, int B,
     return PSH_OK;
 }
 
+int psh_calibrate_workspace_bytes(int B, int k, int nT, size_t* out) {
+    if (!out || B <= 0 || k <= 0 || nT <= 0) return PSH_ERR_ARG;
+    if (k > PSH_MAX_K || nT > PSH_CAL_MAX_INSTRUMENTS) return PSH_ERR_UNSUPPORTED;
+    *out = (size_t)B * (nT + 1) * k * sizeof(double);                      // the terminal prices; a_i / e_i of a trial
+    return PSH_OK;
+}
+
+int psh_calibrate_weights(int device, void* stream, const float* dlnx, int64_t row_stride, int B, int k, int len,
+                          const double* prior, double x_init, double rate, const int* Ts, int nT, const double* strike,
+                          const double* target, int nM, int kind, int martingale, double eps, double tol, int max_iter,
+                          double* out_weights, double* out_lambda, double* out_model, double* out_info, int32_t* out_status,
+                          void* workspace, size_t workspace_bytes) {
+    if (!dlnx || !Ts || !strike || !target || !out_weights || !out_lambda || !out_model || !out_info || !out_status ||
+        !workspace || B <= 0 || k <= 0 || len <= 0 || row_stride < len || nT <= 0 || nM <= 0 || kind < PSH_HMC_OTM ||
+        kind > PSH_HMC_PUT || !std::isfinite(x_init) || !(x_init > 0.0) || !std::isfinite(rate) || !(eps >= 0.0) ||
+        !std::isfinite(eps) || !(tol > 0.0) || max_iter < 0)
+        return PSH_ERR_ARG;
+    for (int i = 0; i < nT; ++i)
+        if (Ts[i] < 1 || Ts[i] > len) return PSH_ERR_ARG;
+    const int64_t J = (int64_t)nT * nM + (martingale ? nT : 0);
+    if (k > PSH_MAX_K || J > PSH_CAL_MAX_INSTRUMENTS) return PSH_ERR_UNSUPPORTED;
+    if ((int64_t)B * k * row_stride >= ((int64_t)1 << 40) || (int64_t)B * ((k + 255) / 256) >= ((int64_t)1 << 31))
+        return PSH_ERR_UNSUPPORTED;
+    size_t need = 0;
+    psh_calibrate_workspace_bytes(B, k, nT, &need);
+    if (workspace_bytes < need) return PSH_ERR_WORKSPACE;
+    CalArgs a{};
+    a.x = dlnx; a.row_stride = row_stride; a.B = B; a.k = k; a.len = len; a.prior = prior; a.x_init = x_init;
+    a.inv_x = 1.0 / x_init; a.eps = eps; a.tol = tol; a.max_iter = max_iter; a.nT = nT; a.nM = nM; a.kind = kind;
+    a.J = (int)J;
+    const double rho = rate / 252.0;
+    for (int i = 0; i < nT; ++i) {
+        a.Ts[i] = Ts[i];
+        a.Tmax = std::max(a.Tmax, Ts[i]);
+        a.disc[i] = std::exp(-(rho * (double)Ts[i]));
+        a.fwd[i] = x_init * std::exp(rho * (double)Ts[i]);
+    }
+    a.strike = strike; a.target = target; a.w = out_weights; a.lam = out_lambda; a.model = out_model; a.info = out_info;
+    a.status = out_status; a.st = (double*)workspace;
+    GUARD_DEVICE(device);
+    HIP_TRY(launch_calibrate(a, (hipStream_t)stream));
+    return PSH_OK;
+}
+
 // what every hedged Monte Carlo entry point asks of the paths, the grid of maturities and strikes and the regression
 static int hmc_check_sizes(const float* dlnx, int64_t row_stride, int B, int k, int len, double x_init, double rate, const int* Ts,
                            int nT, const double* Ms, int nM, int degree, int kind) {

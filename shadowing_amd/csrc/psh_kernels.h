@@ -442,6 +442,24 @@ struct WeightsArgs {
 };
 hipError_t launch_softmax_weights(const WeightsArgs& a, hipStream_t s);
 
+// psh_calibrate.hip: the paths' weights calibrated to quoted vanillas (psh_calibrate_weights)
+struct CalArgs {
+    const float* x;           // log-returns, row (b * k + i) at x + (b * k + i) * row_stride
+    int64_t row_stride;
+    int B, k, len;
+    const double* prior;      // (B, k) or NULL: unit weights
+    double x_init, inv_x;     // inv_x = 1 / x_init, formed on the host
+    double eps, tol;
+    int max_iter, nT, nM, kind, J, Tmax;
+    int Ts[32];               // nT <= J <= PSH_CAL_MAX_INSTRUMENTS = 32
+    double disc[32], fwd[32];  // exp(-rho T), x_init exp(rho T) per maturity
+    const double *strike, *target;                                        // (B, nT, nM)
+    double *w, *lam, *model, *info;                                       // (B, k), (B, J), (B, J), (B, 4)
+    int32_t* status;                                                      // (B,)
+    double* st;               // workspace: (B, nT, k) terminal prices
+};
+hipError_t launch_calibrate(const CalArgs& a, hipStream_t s);
+
 // psh_hmc.hip: hedged Monte Carlo on the shadowing paths of a date (psh_hedged_mc)
 #define PSH_HMC_SG 3              // strikes a block solves (the Gram matrix of a step is shared by them)
 #define PSH_HMC_MAX_T 64

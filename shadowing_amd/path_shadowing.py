@@ -1046,24 +1046,105 @@ class PathShadowing:
 
     def smile_from_paths(self, distances: np.ndarray, paths, Ts, Ms, proba_name: str = "softmax", eta: float | None = None,
                          r: float = 0.0, x_init: float = 100.0, channel: int = 0, degree: int = 3, kind: str = "otm",
-                         report: bool = False):
+                         report: bool = False, calibrate_to=None):
         """Hedged Monte Carlo smile (pricing.compute_smile) of the out-context of the k shadowing paths of every query,
         weighted by the averaging class, as predict_from_paths() weighs its statistic.  `paths` (B, k, C, T_x + h) are
         log-returns; prices start at x_init.  Numpy paths take the host path, HIP tensors the psh_hedged_mc kernel.
-        report=True: the Smile's report fields (delta, risk, standard errors, policy) are filled."""
+        report=True: the Smile's report fields (delta, risk, standard errors, policy) are filled.  calibrate_to=MarketQuotes:
+        the averaging weights are the prior of calibration.calibrate_from_log_returns and the smile is priced under the
+        calibrated ones (`Smile.calibration`)."""
         if not isinstance(self.context, PredictionContext):
             raise NotImplementedError("smile_from_paths: only a PredictionContext has an out-context to price on")
-        from .pricing import smile_from_log_returns
         future = self.context.select_out_context(paths)[:, :, channel, :]
         d = distances.detach().cpu().numpy() if isinstance(distances, torch.Tensor) else np.asarray(distances)
         w = self._smile_weights(proba_name, d, eta)
         cuda = isinstance(future, torch.Tensor) and future.is_cuda
-        return smile_from_log_returns(future, w, Ts, Ms, x_init, r, degree=degree, kind=kind, cuda=cuda, report=report)
+        return self._smile_under(future, w, Ts, Ms, x_init, r, degree, kind, cuda, report, calibrate_to)
+
+    @staticmethod
+    def _smile_under(future, w, Ts, Ms, x_init, r, degree, kind, cuda, report, calibrate_to):
+        """The smile of the out-context log-returns under the weights w, or, given quotes, under w calibrated to them."""
+        from .pricing import smile_from_log_returns
+        if calibrate_to is None:
+            return smile_from_log_returns(future, w, Ts, Ms, x_init, r, degree=degree, kind=kind, cuda=cuda, report=report)
+        from .calibration import calibrate_from_log_returns
+        cal = calibrate_from_log_returns(future, w, calibrate_to, x_init, r, cuda=cuda)
+        sm = smile_from_log_returns(future, cal.weights, Ts, Ms, x_init, r, degree=degree, kind=kind, cuda=cuda, report=report)
+        sm.calibration = cal
+        return sm
+
+    def calibrate_from_paths(self, distances: np.ndarray, paths, quotes, proba_name: str = "softmax", eta: float | None = None,
+                             r: float = 0.0, x_init: float = 100.0, channel: int = 0, eps: float = 1e-6, tol: float = 1e-8,
+                             martingale: bool = True):
+        """The weights of the k shadowing paths of every query calibrated to `quotes` (calibration.MarketQuotes), the prior
+        being the averaging class's weights: a calibration.Calibration.  Numpy paths take the numpy twin, HIP tensors the
+        psh_calibrate_weights kernel."""
+        if not isinstance(self.context, PredictionContext):
+            raise NotImplementedError("calibrate_from_paths: only a PredictionContext has an out-context to price on")
+        from .calibration import calibrate_from_log_returns
+        future = self.context.select_out_context(paths)[:, :, channel, :]
+        d = distances.detach().cpu().numpy() if isinstance(distances, torch.Tensor) else np.asarray(distances)
+        w = self._smile_weights(proba_name, d, eta)
+        cuda = isinstance(future, torch.Tensor) and future.is_cuda
+        return calibrate_from_log_returns(future, w, quotes, x_init, r, eps=eps, tol=tol, martingale=martingale, cuda=cuda)
+
+    def calibrate(self, x_context: ArrayType, k: int, quotes, eta: float | None = None, proba_name: str = "softmax",
+                  r: float = 0.0, x_init: float = 100.0, channel: int = 0, eps: float = 1e-6, tol: float = 1e-8,
+                  martingale: bool = True, n_dataset_splits: int = 1, n_context_splits: int = 1, cuda: bool = False,
+                  device_weights: bool = False):
+        """shadow() + calibrate_from_paths() over `n_context_splits` batches of queries (README "Calibrating to market
+        quotes").  With cuda=True on a natively scanned configuration the out-context view of the gathered paths stays in
+        HBM: the prior is formed by psh_softmax_weights on the scan's device distances (device_weights=True) or on the host
+        and uploaded, as smile() does; psh_calibrate_weights runs on the view, and `Calibration.weights` is a HIP tensor
+        (B, k) that the device-side consumers take as it is.  Any other route (k > PSH_MAX_K included) takes the numpy
+        twin.  Quotes that differ by date, (B, nT, nM), follow the queries through the splits."""
+        from .calibration import concat_calibrations, calibrate_from_log_returns
+        if not isinstance(self.context, PredictionContext):
+            raise NotImplementedError("calibrate: only a PredictionContext has an out-context to price on")
+        seen = [0]
+
+        def batch_quotes(n):
+            q = quotes.rows(slice(seen[0], seen[0] + n))
+            seen[0] += n
+            return q
+
+        def on_host(xr):
+            d, paths, _ = self.shadow(xr, k, n_dataset_splits, cuda)
+            self.last_weights = "host"
+            return self.calibrate_from_paths(d, paths, batch_quotes(xr.shape[0]), proba_name, eta, r, x_init, channel, eps, tol,
+                                             martingale)
+
+        def on_device(xr, y):
+            future, wt = self._device_prior(xr, y, k, proba_name, eta, channel, device_weights)
+            return calibrate_from_log_returns(future, wt, batch_quotes(xr.shape[0]), x_init, r, eps=eps, tol=tol,
+                                              martingale=martingale, cuda=True)
+
+        return concat_calibrations(self._over_context_splits(x_context, k, n_context_splits, cuda, k <= _native.PSH_MAX_K,
+                                                             on_host, on_device))
+
+    def _device_prior(self, xr, y, k: int, proba_name: str, eta: float | None, channel: int, device_weights: bool):
+        """What smile() and calibrate() begin with on the device route: (the out-context view of the gathered paths of one
+        channel, the averaging weights as a HIP tensor or None for uniform ones), the weights formed on the device
+        (device_weights) or on the host and uploaded; `last_weights` says which."""
+        reduce, held = None, {}
+        if device_weights:
+            eta_dev = self._device_eta(proba_name, eta)
+
+            def reduce(future, d):
+                held["w"] = _native.softmax_weights(d, [eta_dev])[0]
+                return ()                                         # (the consumer brings its own results down)
+
+        future, host, reduced = self._scan_and_evaluate(xr, y, k, lambda out_context: out_context[:, :, channel, :], reduce)
+        self.last_weights = "device" if reduced else "host"
+        if reduced:
+            return future, held["w"]
+        w = self._smile_weights(proba_name, host[0], eta)
+        return future, None if w is None else torch.from_numpy(w.copy()).to(future.device)
 
     def smile(self, x_context: ArrayType, k: int, Ts, Ms, eta: float | None = None, proba_name: str = "softmax",
               r: float = 0.0, x_init: float = 100.0, channel: int = 0, degree: int = 3, kind: str = "otm",
               n_dataset_splits: int = 1, n_context_splits: int = 1, cuda: bool = False, report: bool = False,
-              device_weights: bool = False):
+              calibrate_to=None, device_weights: bool = False):
         """shadow() + smile_from_paths() over `n_context_splits` batches of queries.  With cuda=True on a natively scanned
         configuration the gathered paths stay in HBM: the (B, k) distances come to the host for the averaging class's
         weights, the weights go back up, psh_hedged_mc prices on the out-context view of the paths, and only the
@@ -1071,33 +1152,22 @@ class PathShadowing:
         report=True: the fit keeps its policy and psh_hedge_replay replays it on the same view -- the paths and the policy
         (Smile.policy.coef, a HIP tensor) stay in HBM, the (B, nT, nM) report fields come down.  device_weights=True on
         that route: psh_softmax_weights forms the weights on the scan's device distances; neither crosses PCIe
-        (`last_weights`)."""
-        from .pricing import concat_smiles, smile_from_log_returns
+        (`last_weights`).  calibrate_to=MarketQuotes (shared by the dates): those weights are the prior, calibrated to the
+        quotes where they lie (psh_calibrate_weights on that route), and the smile is priced under the calibrated weights;
+        `Smile.calibration` holds the Calibration."""
+        from .pricing import concat_smiles
         if not isinstance(self.context, PredictionContext):
             raise NotImplementedError("smile: only a PredictionContext has an out-context to price on")
 
         def on_host(xr):
             d, paths, _ = self.shadow(xr, k, n_dataset_splits, cuda)
             self.last_weights = "host"
-            return self.smile_from_paths(d, paths, Ts, Ms, proba_name, eta, r, x_init, channel, degree, kind, report)
+            return self.smile_from_paths(d, paths, Ts, Ms, proba_name, eta, r, x_init, channel, degree, kind, report,
+                                         calibrate_to)
 
         def on_device(xr, y):
-            reduce, held = None, {}
-            if device_weights:
-                eta_dev = self._device_eta(proba_name, eta)
-
-                def reduce(future, d):
-                    held["w"] = _native.softmax_weights(d, [eta_dev])[0]
-                    return ()                                         # (the pricing brings its own results down)
-
-            future, host, reduced = self._scan_and_evaluate(xr, y, k, lambda out_context: out_context[:, :, channel, :], reduce)
-            self.last_weights = "device" if reduced else "host"
-            if reduced:
-                wt = held["w"]
-            else:
-                w = self._smile_weights(proba_name, host[0], eta)
-                wt = None if w is None else torch.from_numpy(w.copy()).to(future.device)
-            return smile_from_log_returns(future, wt, Ts, Ms, x_init, r, degree=degree, kind=kind, cuda=True, report=report)
+            future, wt = self._device_prior(xr, y, k, proba_name, eta, channel, device_weights)
+            return self._smile_under(future, wt, Ts, Ms, x_init, r, degree, kind, True, report, calibrate_to)
 
         return concat_smiles(self._over_context_splits(x_context, k, n_context_splits, cuda, k <= _native.PSH_MAX_K,
                                                        on_host, on_device))

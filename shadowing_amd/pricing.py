@@ -114,6 +114,8 @@ class Smile:
     iv_se: np.ndarray | None = None
     n_eff: np.ndarray | None = None
     policy: "HedgePolicy | None" = None
+    # calibrate_to=MarketQuotes (None otherwise): the calibration.Calibration whose weights the smile was priced under
+    calibration: object = None
 
     def plot(self, ax=None, rescale: bool = True, legend: bool = True, color=None, errorbars: bool = False, **kw):
         """Implied vol against M (rescale=True) or against log(K / F), F the forward (rescale=False): one line per
@@ -509,6 +511,9 @@ def concat_smiles(parts: list) -> Smile:
         coefs = [p.policy.coef for p in parts]
         coef = torch.cat(coefs) if isinstance(coefs[0], torch.Tensor) else np.concatenate(coefs)
         sm.policy = HedgePolicy(coef, sm.strikes, sm.prices, sm.Ts, sm.Ms, p0.kind, p0.policy.degree, p0.x_init, p0.r, sm.status)
+    if p0.calibration is not None:
+        from .calibration import concat_calibrations
+        sm.calibration = concat_calibrations([p.calibration for p in parts])
     return sm
 
 
