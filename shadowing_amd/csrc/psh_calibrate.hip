@@ -73,6 +73,7 @@
 
 #include "psh.h"
 #include "psh_kernels.h"
+#include "psh_wave.h"
 
 namespace psh {
 
@@ -122,29 +123,6 @@ __device__ __forceinline__ double cal_g(double S, double K, double disc, int sgn
     return disc * pay;
 }
 
-// the fixed trees: a butterfly over the wave, then the waves in order; every thread returns the same number
-__device__ __forceinline__ double cal_block_sum(double v, double* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = red[0];
-    for (int u = 1; u < CAL_WAVES; ++u) s = s + red[u];
-    __syncthreads();
-    return s;
-}
-
-__device__ __forceinline__ double cal_block_max(double v, double* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = red[0];
-    for (int u = 1; u < CAL_WAVES; ++u) s = fmax(s, red[u]);
-    __syncthreads();
-    return s;
-}
-
 struct CalShared {
     double hs[PSH_CAL_MAX_INSTRUMENTS * CAL_CH];   // the tile of h: hs[j * CAL_CH + path of the tile]
     double qs[CAL_CH];                             // q of the tile's paths
@@ -175,7 +153,7 @@ __device__ __forceinline__ double cal_args(const CalArgs& a, CalShared& sh, cons
         m = fmax(m, s);
         ab[i] = s;
     }
-    return cal_block_max(m, sh.red);
+    return block_reduce<CAL_WAVES, true>(m, sh.red, WaveMax{});
 }
 
 __global__ __launch_bounds__(CAL_THREADS) void cal_newton_kernel(CalArgs a) {
@@ -220,7 +198,7 @@ __global__ __launch_bounds__(CAL_THREADS) void cal_newton_kernel(CalArgs a) {
             if (s0 != s0) bad_r = 1;
         }
     }
-    const double P = cal_block_sum(psum, sh.red);          // (its barriers also publish the instruments)
+    const double P = block_reduce<CAL_WAVES, true>(psum, sh.red, WaveSum{});          // (its barriers also publish the instruments)
     if (!(P > 0.0) || !isfinite(P)) bad_w = 1;
     int status = (__syncthreads_or(bad_r) ? PSH_CAL_STATUS_NONFINITE : 0);
     status |= (__syncthreads_or(bad_w) ? PSH_CAL_STATUS_WEIGHTS : 0);
@@ -248,8 +226,8 @@ __global__ __launch_bounds__(CAL_THREADS) void cal_newton_kernel(CalArgs a) {
             ab[i] = e;
             zs = zs + e;
         }
-        const double Z = cal_block_sum(zs, sh.red);
-        kout = cal_block_sum(ks, sh.red);
+        const double Z = block_reduce<CAL_WAVES, true>(zs, sh.red, WaveSum{});
+        kout = block_reduce<CAL_WAVES, true>(ks, sh.red, WaveSum{});
         double l2 = 0.0;
         for (int j = 0; j < J; ++j) l2 = l2 + sh.trial[j] * sh.trial[j];
         zout = Z;
@@ -310,16 +288,14 @@ __global__ __launch_bounds__(CAL_THREADS) void cal_newton_kernel(CalArgs a) {
                 }
             }
             if (mine) {
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) { mu0 = mu0 + __shfl_xor(mu0, o); mu1 = mu1 + __shfl_xor(mu1, o); }
+                mu0 = wave_sum(mu0);
+                mu1 = wave_sum(mu1);
                 if (lane == 0 && sh.act[r0]) sh.mu[r0] = mu0;
                 if (lane == 0 && r1 >= 0 && sh.act[r1]) sh.mu[r1] = mu1;
 #pragma unroll
                 for (int l = 0; l < PSH_CAL_MAX_INSTRUMENTS; ++l) {
                     if (l > r0) continue;
-                    double v0 = acc0[l], v1 = acc1[l];
-#pragma unroll
-                    for (int o = 32; o > 0; o >>= 1) { v0 = v0 + __shfl_xor(v0, o); v1 = v1 + __shfl_xor(v1, o); }
+                    const double v0 = wave_sum(acc0[l]), v1 = wave_sum(acc1[l]);
                     if (lane == 0) sh.Hs[r0 * CAL_LD + l] = v0;
                     if (lane == 0 && l <= r1) sh.Hs[r1 * CAL_LD + l] = v1;
                 }
@@ -413,7 +389,7 @@ __global__ __launch_bounds__(CAL_THREADS) void cal_newton_kernel(CalArgs a) {
         q2 = q2 + q * q;
     }
     const double kl = ksum / Z - lnzp;
-    const double s2 = cal_block_sum(q2, sh.red);
+    const double s2 = block_reduce<CAL_WAVES, true>(q2, sh.red, WaveSum{});
     for (int j = wave; j < J; j += CAL_WAVES) {
         double m = 0.0;
 #pragma unroll 4
@@ -422,8 +398,7 @@ __global__ __launch_bounds__(CAL_THREADS) void cal_newton_kernel(CalArgs a) {
             const double S = p > 0.0 ? st[(int64_t)i * a.nT + sh.q[j]] : a.x_init;
             m = m + outw[i] * cal_g(S, sh.K[j], sh.disc[j], sh.sgn[j]);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = m + __shfl_xor(m, o);
+        m = wave_sum(m);
         if (lane == 0) a.model[b * J + j] = m;
     }
     if (tid < J) a.lam[b * J + tid] = sh.lam[tid];

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "psh_kernels.h"
+#include "psh_wave.h"
 
 namespace psh {
 
@@ -350,36 +351,6 @@ __device__ __forceinline__ int mq8_quant(float xv, float inv_s0) {
     const int q = (int)rintf(xv * inv_s0);
     return q > 127 ? 127 : (q < -127 ? -127 : q);
 }
-// The maximum of a non-negative value over the wave, in every lane (uniform): four DPP steps inside the rows of 16 lanes, then the
-// four rows through SGPRs -- no trip through the LDS crossbar (six dependent ds_bpermute are ~100+ cycles each beside a busy LDS).
-__device__ __forceinline__ float wave_max_nonneg(float x) {
-    // (as integers: non-negative floats order like their bit patterns, and an integer maximum needs no quieting of its operands
-    //  -- fmaxf() cost a v_max x, x per operand and kept the DPP move a separate instruction; old = 0 with bound_ctrl lets the
-    //  compiler fold the move into the v_max_i32 itself)
-    int v = __float_as_int(x);
-    auto step = [&](int moved) { v = v > moved ? v : moved; };
-    step(__builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true));     // quad_perm [1, 0, 3, 2]
-    step(__builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true));     // quad_perm [2, 3, 0, 1]
-    step(__builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, true));    // row_half_mirror
-    step(__builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, true));    // row_mirror
-    const int r0 = __builtin_amdgcn_readlane(v, 0), r1 = __builtin_amdgcn_readlane(v, 16);
-    const int r2 = __builtin_amdgcn_readlane(v, 32), r3 = __builtin_amdgcn_readlane(v, 48);
-    const int m01 = r0 > r1 ? r0 : r1, m23 = r2 > r3 ? r2 : r3;
-    return __int_as_float(m01 > m23 ? m01 : m23);
-}
-// The sum of a value over the wave, in every lane (uniform), the same way: pairs, quads, half rows, rows by DPP, the four rows
-// through SGPRs.  (The order of the additions is not the lane order: callers that bound a rounding error allow for any order.)
-__device__ __forceinline__ float wave_sum_dpp(float x) {
-    int v = __float_as_int(x);
-    auto step = [&](int moved) { v = __float_as_int(__int_as_float(v) + __int_as_float(moved)); };
-    step(__builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true));     // quad_perm [1, 0, 3, 2]
-    step(__builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true));     // quad_perm [2, 3, 0, 1]
-    step(__builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, true));    // row_half_mirror
-    step(__builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, true));    // row_mirror
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(v, 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(v, 16));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(v, 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(v, 48));
-    return (r0 + r1) + (r2 + r3);
-}
 // inc += (inc of the lane CTRL names, 0 where there is none): one step of a wave scan, a v_add_f32 with a DPP operand
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ float dpp_add(float inc) {
@@ -451,8 +422,7 @@ __device__ __forceinline__ void emit16(const ScanArgs& a, int b, const float (&a
 #pragma unroll
         for (int i = 0; i < PSH_L; ++i) m = (i < nvalid) ? fminf(m, acc[i]) : m;
         if (a.boot_per_wave) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) m = fminf(m, __shfl_xor(m, off, 64));
+            m = wave_min(m);
             if (lane == 0) a.minbuf[(int64_t)b * a.min_stride + (int64_t)rs] = m;
         } else {
             a.minbuf[(int64_t)b * a.min_stride + (int64_t)rs * 64 + lane] = m;

@@ -386,8 +386,7 @@ __global__ __launch_bounds__(THREADS) void embed_scan_kernel(ScanArgs a) {
         const int q_end = (q_begin + a.q_per_group) < a.B ? (q_begin + a.q_per_group) : a.B;
 
         if (MODE != PSH_MODE_ALL && nested) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) ymax = fmaxf(ymax, __shfl_xor(ymax, off, 64));
+            ymax = wave_max(ymax);
             const float err = ymax * cerr;                    // radius of the cheap embedding around the exact one
             const int base = PSH_L * lane;
             int ns = 0;                                       // survivors waiting in sl (wave-uniform)
@@ -414,8 +413,7 @@ __global__ __launch_bounds__(THREADS) void embed_scan_kernel(ScanArgs a) {
                     const int nA4 = lv ? ((gA.y + 3) & ~3) : 0, nB4 = (lv && hasB) ? ((gB.y + 3) & ~3) : 0;
                     auto chain = [&](int lo, int n4, int ath, float c) -> float {
                         int lm = n4;
-#pragma unroll
-                        for (int off = 32; off > 0; off >>= 1) { const int o2 = __shfl_xor(lm, off, 64); lm = o2 > lm ? o2 : lm; }
+                        lm = wave_max(lm);
                         lm = __builtin_amdgcn_readfirstlane(lm);
                         float hy = 0.0f;
 #pragma unroll 1
@@ -551,8 +549,7 @@ __global__ __launch_bounds__(THREADS) void embed_scan_kernel(ScanArgs a) {
 #pragma unroll
                         for (int w = 0; w < PSH_L; ++w) m = (w < nvalid) ? fminf(m, acc[g][w & 7][w >> 3]) : m;
                         if (a.boot_per_wave) {
-#pragma unroll
-                            for (int off = 32; off > 0; off >>= 1) m = fminf(m, __shfl_xor(m, off, 64));
+                            m = wave_min(m);
                         }
                         const float su = __builtin_sqrtf(m) * (1.0f + 1.0f / 32768.0f) + err;
                         const float ub = su * su * (1.0f + 1.0f / 16384.0f);
@@ -773,8 +770,7 @@ __global__ __launch_bounds__(PSH_ROWS_THREADS) void rows_kernel(ScanArgs a, int 
                     // says as much as its 64 values (two of the best rows in one chunk: the estimate comes out a shade
                     // higher), and the threshold kernel selects among 64x fewer entries
                     float m = (valid && acc == acc) ? acc : __uint_as_float(PSH_INF_BITS);
-#pragma unroll
-                    for (int off = 32; off > 0; off >>= 1) m = fminf(m, __shfl_xor(m, off, 64));
+                    m = wave_min(m);
                     if (lane == 0) a.minbuf[(int64_t)b * a.min_stride + c] = m;
                 } else if (valid) a.minbuf[(int64_t)b * a.min_stride + i] = acc;
             } else if (MODE == PSH_MODE_ALL) {               // exhaustive path: one slot per row of the chunk

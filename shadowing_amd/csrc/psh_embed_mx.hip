@@ -900,8 +900,7 @@ __global__ __launch_bounds__(PSH_EMX_THREADS) void embed_mx_kernel(ScanArgs a) {
 #pragma unroll
                 for (int sl = 1; sl < 8; ++sl) mn = fminf(mn, vslot(sl));
                 if (MODE == PSH_MODE_BOOT) {
-#pragma unroll
-                    for (int off = 32; off > 0; off >>= 1) mn = fminf(mn, __shfl_xor(mn, off, 64));
+                    mn = wave_min(mn);
                     // one minimum per HALF segment (the launch plan's boot_per_wave == 2): an upper bound of the exact acc of
                     // the half's best window
                     float m2 = mn + nx;

@@ -214,9 +214,7 @@ __global__ __launch_bounds__(PSH_PLAN_THREADS) void embed_plan_kernel(const floa
             key = __builtin_amdgcn_readlane(key, 63);
             if ((key & 63) == tid) { load += s_t4[i]; s_bin[i] = tid; }
         }
-        int lmax = load;
-#pragma unroll
-        for (int o2 = 32; o2 > 0; o2 >>= 1) { const int v2 = __shfl_xor(lmax, o2, 64); lmax = v2 > lmax ? v2 : lmax; }
+        const int lmax = wave_max(load);
         if (tid == 0) { s_nl = NL; s_lmax = lmax; plan->vnl = NL; plan->vmax = 4 * lmax; }
     }
     __syncthreads();
@@ -597,10 +595,8 @@ __global__ __launch_bounds__(THREADS) void embed_px_kernel(ScanArgs a) {
                         hgt[g] = (int)__float_as_uint(sum * rsm);
                     }
                     hq[g * 64 + lane] = __uint_as_float((unsigned)hgt[g]);   // the same coordinates by row, for the sparse second phase
-#pragma unroll
-                    for (int off = 32; off > 0; off >>= 1) { vs += __shfl_xor(vs, off, 64); sq += __shfl_xor(sq, off, 64); }
-                    Vq[g] = vs * (1.0f + 1.0f / 256.0f);
-                    hnq[g] = 6.0f * 5.9604645e-8f * 1.001f * __builtin_sqrtf(sq);
+                    Vq[g] = wave_sum(vs) * (1.0f + 1.0f / 256.0f);
+                    hnq[g] = 6.0f * 5.9604645e-8f * 1.001f * __builtin_sqrtf(wave_sum(sq));
                 }
                 wave_lds_fence();
             }
@@ -780,8 +776,7 @@ __global__ __launch_bounds__(THREADS) void embed_px_kernel(ScanArgs a) {
 #pragma unroll
                     for (int w = 0; w < PSH_L; ++w) m = ((vmask >> w) & 1u) ? fminf(m, acc[g][w >> 1][w & 1]) : m;
                     if (a.boot_per_wave) {
-#pragma unroll
-                        for (int off = 32; off > 0; off >>= 1) m = fminf(m, __shfl_xor(m, off, 64));
+                        m = wave_min(m);
                     }
                     const float su = __builtin_sqrtf(m + Vq[g]) * (1.0f + 1.0f / 32768.0f) + errq;
                     const float ub = su * su * (1.0f + 1.0f / 16384.0f);

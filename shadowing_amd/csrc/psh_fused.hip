@@ -191,8 +191,7 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_fused_kernel(ScanArgs a
             float m = __uint_as_float(PSH_INF_BITS);
 #pragma unroll
             for (int i = 0; i < PSH_L; ++i) m = (i < nvalid) ? fminf(m, acc[i]) : m;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) m = fminf(m, __shfl_xor(m, off, 64));
+            m = wave_min(m);
             if (!(m == m)) m = __uint_as_float(PSH_INF_BITS);                  // NaN data: the segment carries no information
             if (lane == 0) store_sc1(&hdr->minima[u], __float_as_uint(m));     // write-through; the block's flag follows the drain
             wave_lds_fence();
@@ -294,13 +293,8 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_fused_kernel(ScanArgs a
             for (int e = 0; e < 4; ++e)
                 if (4 * tid + e < nbu && mv[e] < PSH_INF_BITS) { kmin = mv[e] < kmin ? mv[e] : kmin; kmax = mv[e] > kmax ? mv[e] : kmax; ++nfin; }
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const unsigned l2 = __shfl_xor(kmin, off, 64), h2 = __shfl_xor(kmax, off, 64);
-            kmin = l2 < kmin ? l2 : kmin;
-            kmax = h2 > kmax ? h2 : kmax;
-            nfin += __shfl_xor(nfin, off, 64);
-        }
+        wave_minmax(kmin, kmax);
+        nfin = wave_sum(nfin);
         if (lane == 0) {
             atomicMin(reinterpret_cast<unsigned*>(&ctl[C_KMIN]), kmin);
             atomicMax(reinterpret_cast<unsigned*>(&ctl[C_KMAX]), kmax);
@@ -331,31 +325,9 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_fused_kernel(ScanArgs a
         }
         __syncthreads();
         if (wave == 0) {
-            constexpr int PER = PSH_FUSED_HIST / 64;
-            unsigned h[PER];
-            unsigned sl = 0;
-#pragma unroll
-            for (int q = 0; q < PER; ++q) { h[q] = hist[PER * lane + q]; sl += h[q]; }
-            unsigned inc = sl;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const unsigned t2 = __shfl_up(inc, off, 64);
-                if (lane >= off) inc += t2;
-            }
-            unsigned cum = inc - sl;
-            const unsigned rk = (unsigned)f.rank;
-            if (cum < rk && inc >= rk) {                                      // exactly one lane
-                int bucket = PER * lane;
-#pragma unroll
-                for (int q = 0; q < PER; ++q) {
-                    if (cum < rk && cum + h[q] >= rk) bucket = PER * lane + q;
-                    cum += h[q];
-                }
-                // every minimum in buckets <= `bucket` is at or below the bucket's upper edge, and there are >= rank of them
-                u64 edge = (u64)kmin + (((u64)bucket + 1ull) << shift) - 1ull;
-                if (edge > (u64)kmax) edge = kmax;
-                ctl[C_EDGE] = (int)(unsigned)edge;
-            }
+            rank_bucket<PSH_FUSED_HIST / 64>(hist, lane, (unsigned)f.rank, [&](const RankBucket& rb) {
+                ctl[C_EDGE] = (int)bucket_upper_edge(kmin, kmax, rb.bucket, shift);
+            });
             wave_lds_fence();
             if (lane == 0) derive_levels(__uint_as_float((unsigned)ctl[C_EDGE]) * PSH_TAU_MARGIN);
         }
@@ -500,18 +472,12 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_fused_kernel(ScanArgs a
         wave_lds_fence();
 #pragma unroll
         for (int i = 0; i < PSH_FUSED_MAX_BLOCKS / 64; ++i) { c4[i] = cnts[(PSH_FUSED_MAX_BLOCKS / 64) * lane + i]; mine += c4[i]; }
-        int inc = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int t2 = __shfl_up(inc, off, 64);
-            if (lane >= off) inc += t2;
-        }
+        const int inc = wave_scan_inclusive(mine, lane);
         int run = inc - mine;
 #pragma unroll
         for (int i = 0; i < PSH_FUSED_MAX_BLOCKS / 64; ++i) { offs[(PSH_FUSED_MAX_BLOCKS / 64) * lane + i] = run; run += c4[i]; }
         tot = __shfl(inc, 63, 64);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) ovf |= __shfl_xor(ovf, off, 64);
+        ovf = wave_or(ovf);
         if (lane == 0) { offs[PSH_FUSED_MAX_BLOCKS] = tot; ctl[C_NTOTAL] = tot; ctl[C_ANYOVF] = ovf; }
     }
     __syncthreads();
@@ -580,14 +546,7 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_fused_kernel(ScanArgs a
                 }
 #pragma unroll
                 for (int jj = 0; jj < 8; jj += 2) {
-                    int v = c[jj] | (c[jj + 1] << 16);      // <= 8 per lane and counter
-                    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);
-                    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);
-                    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);
-                    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);
-                    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, true);
-                    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, true);
-                    v = __builtin_amdgcn_readlane(v, 63);
+                    const int v = wave_total_dpp(c[jj] | (c[jj + 1] << 16));      // <= 8 per lane and counter
                     if (lane == 0) {
                         if (j0 + jj < mown && (v & 0xffff)) atomicAdd(&rankc[j0 + jj], v & 0xffff);
                         if (j0 + jj + 1 < mown && (v >> 16)) atomicAdd(&rankc[j0 + jj + 1], v >> 16);

@@ -9,6 +9,7 @@
 
 #include "psh.h"
 #include "psh_kernels.h"
+#include "psh_wave.h"
 
 namespace psh {
 
@@ -19,29 +20,14 @@ namespace psh {
 
 namespace {
 
-__device__ __forceinline__ double hmc_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double hmc_wave_min(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
-    return v;
-}
-__device__ __forceinline__ double hmc_wave_max(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
-// tot[q] = sum over the block of v[q]: wave butterflies, then the waves in order.  Ends with a barrier.
+// tot[q] = sum over the block of v[q]: wave butterflies, then the waves in order from 0.0 (block_reduce of psh_wave.h starts
+// at the first wave's sum: the two differ in the sign of a zero total).  Ends with a barrier.
 template <int N>
 __device__ __forceinline__ void block_sum(const double (&v)[N], double* red, double* tot) {
     const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
 #pragma unroll
     for (int q = 0; q < N; ++q) {
-        const double s = hmc_wave_sum(v[q]);
+        const double s = wave_sum(v[q]);
         if (lane == 0) red[wave * N + q] = s;
     }
     __syncthreads();
@@ -178,8 +164,8 @@ __device__ __forceinline__ void hmc_body(const HmcArgs& a, double* policy) {
                 mn = fmin(mn, S);
                 mx = fmax(mx, S);
             }
-            mn = hmc_wave_min(mn);
-            mx = hmc_wave_max(mx);
+            mn = wave_min(mn);
+            mx = wave_max(mx);
             if (lane == 0) {
                 red[PSH_HMC_WAVES * 2 + (tid >> 6)] = mn;
                 red[PSH_HMC_WAVES * 3 + (tid >> 6)] = mx;

@@ -416,6 +416,8 @@ struct QuantileArgs {
 };
 hipError_t launch_quantiles(const QuantileArgs& a, hipStream_t s);
 
+#define PSH_SMALL_GRID_CUS 256   // compute units a small grid is spread over (psh_scoring.hip, psh_weights.hip: groups of sets)
+
 // psh_scoring.hip: CRPS, PIT and mean of the k paths against an observation, for every weight set (psh_score_ensemble)
 struct ScoreArgs {
     const float* values;      // (B, k, m)

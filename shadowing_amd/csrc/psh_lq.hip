@@ -102,8 +102,7 @@ __global__ __launch_bounds__(PSH_LQ_THREADS) void scan_lq_kernel(ScanArgs a) {
         const float* xq = xs + (size_t)ql * W;
         unsigned mb = 0u;
         for (int j = lane; j < W; j += 64) mb = max(mb, __float_as_uint(fabsf(xq[j])));
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) mb = max(mb, (unsigned)__shfl_xor((int)mb, off, 64));
+        mb = wave_max(mb);
         if (lane == 0) {
             int sexp = 60;
             bool ok = mb < PSH_INF_BITS;
@@ -294,8 +293,7 @@ __global__ __launch_bounds__(PSH_LQ_THREADS) void scan_lq_kernel(ScanArgs a) {
                     mn = p < nvalid ? fminf(mn, c[r]) : mn;
                 }
             }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) mn = fminf(mn, __shfl_xor(mn, off, 64));
+            mn = wave_min(mn);
             if (lane == 0) {
                 // An upper bound of the smallest acc of the unit, back in the data's scale.  With 2 |c^ - c| <= a (nx~ + E) and
                 // E <= 2 (nx~ + acc~) (stream_threshold's model, read the other way round):

@@ -13,28 +13,22 @@
 #include <stdint.h>
 
 #include "psh_kernels.h"
+#include "psh_wave.h"
 
 namespace psh {
 
-// double sum over the 64 lanes of a wave (result in every lane)
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
+#define PSH_WMOM_THREADS 1024
 
-#define PSH_MOM_THREADS 1024
-
-// One block per (query b, chunk of up to PSH_MOM_THREADS columns).  The (k x m) slab of a query is walked with a stride that
+// One block per (query b, chunk of up to PSH_WMOM_THREADS columns).  The (k x m) slab of a query is walked with a stride that
 // is a multiple of m, so a thread stays on ONE column i = t % m and the slab is read coalesced; per-thread partial sums in
 // double, then the partials of a column are added in a fixed order (deterministic results).
-__global__ __launch_bounds__(PSH_MOM_THREADS) void moments_kernel(MomentsArgs a) {
-    __shared__ double part[PSH_MOM_THREADS];
-    __shared__ double meanL[PSH_MOM_THREADS];
+__global__ __launch_bounds__(PSH_WMOM_THREADS) void moments_kernel(MomentsArgs a) {
+    __shared__ double part[PSH_WMOM_THREADS];
+    __shared__ double meanL[PSH_WMOM_THREADS];
     const int b = (int)blockIdx.x;
-    const int c0 = (int)blockIdx.y * PSH_MOM_THREADS;                       // first column of this chunk
-    const int mc = (a.m - c0) < PSH_MOM_THREADS ? (a.m - c0) : PSH_MOM_THREADS;   // columns of this chunk
-    const int rows_par = PSH_MOM_THREADS / mc;                               // path rows walked side by side
+    const int c0 = (int)blockIdx.y * PSH_WMOM_THREADS;                       // first column of this chunk
+    const int mc = (a.m - c0) < PSH_WMOM_THREADS ? (a.m - c0) : PSH_WMOM_THREADS;   // columns of this chunk
+    const int rows_par = PSH_WMOM_THREADS / mc;                               // path rows walked side by side
     const int t = (int)threadIdx.x;
     const bool live = t < rows_par * mc;
     const int i = live ? t % mc : 0, j0 = live ? t / mc : 0;
@@ -68,8 +62,8 @@ __global__ __launch_bounds__(PSH_MOM_THREADS) void moments_kernel(MomentsArgs a)
 }
 
 hipError_t launch_moments(const MomentsArgs& a, hipStream_t s) {
-    dim3 grid((unsigned)a.B, (unsigned)((a.m + PSH_MOM_THREADS - 1) / PSH_MOM_THREADS));
-    hipLaunchKernelGGL(moments_kernel, grid, dim3(PSH_MOM_THREADS), 0, s, a);
+    dim3 grid((unsigned)a.B, (unsigned)((a.m + PSH_WMOM_THREADS - 1) / PSH_WMOM_THREADS));
+    hipLaunchKernelGGL(moments_kernel, grid, dim3(PSH_WMOM_THREADS), 0, s, a);
     return hipGetLastError();
 }
 
@@ -96,7 +90,7 @@ __global__ __launch_bounds__(PSH_RV_THREADS) void rv_kernel(RvArgs a) {
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             if (q >= nt) break;
-            const double tot = wave_sum_f64(acc[q]);
+            const double tot = wave_sum(acc[q]);
             if (lane == 0) {
                 float r = __fmul_rn((float)(tot / (double)a.Ts[t0 + q]), 252.0f);
                 if (a.vol) r = sqrtf(r);

@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "psh_kernels.h"
+#include "psh_wave.h"
 
 namespace psh {
 
@@ -32,9 +33,7 @@ __global__ __launch_bounds__(256) void count_nonfinite_kernel(const float* __res
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) c += nonfinite(x[(n4 << 2) + threadIdx.x]);
     const unsigned long long m = __ballot(c != 0);
     if (m) {                                             // (rare: a wave that saw none does not touch the counter)
-        unsigned tot = c;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off, 64);
+        const unsigned tot = wave_sum(c);
         if ((threadIdx.x & 63) == 0) atomicAdd(out, (unsigned long long)tot);
     }
 }

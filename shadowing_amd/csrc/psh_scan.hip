@@ -166,8 +166,7 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_kernel(ScanArgs a) {
                     for (int off = 16; off > 0; off >>= 1) m = fminf(m, __shfl_xor(m, off, 64));
                     if ((lane & 31) == 0) a.minbuf[(int64_t)b * a.min_stride + 2 * (int64_t)rs + (lane >> 5)] = m;
                 } else if (a.boot_per_wave) {
-#pragma unroll
-                    for (int off = 32; off > 0; off >>= 1) m = fminf(m, __shfl_xor(m, off, 64));
+                    m = wave_min(m);
                     if (lane == 0) a.minbuf[(int64_t)b * a.min_stride + (int64_t)rs] = m;
                 } else {
                     a.minbuf[(int64_t)b * a.min_stride + (int64_t)rs * 64 + lane] = m;
@@ -232,8 +231,7 @@ __global__ __launch_bounds__(PSH_SCAN_THREADS) void scan_kernel(ScanArgs a) {
             a.bcount[(int64_t)q * PSH_MAX_BLOCKS + blockIdx.x] = lcount[q];
     }
     if (MODE == PSH_MODE_BOOT && a.blockmax) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) wmax = fmaxf(wmax, __shfl_xor(wmax, off, 64));
+        wmax = wave_max(wmax);
         if (lane == 0) atomicMax(reinterpret_cast<unsigned*>(next_unit + 1), __float_as_uint(wmax));   // >= 0: bits order as values
         __syncthreads();
         if (threadIdx.x == 0) a.blockmax[blockIdx.x] = __uint_as_float((unsigned)next_unit[1]);
@@ -1103,8 +1101,7 @@ __global__ __launch_bounds__(1024) void mq_prep_kernel(const float* __restrict__
     __syncthreads();
     unsigned mb = 0u;                                       // the largest |x| of the whole batch into [4, 8)
     for (int64_t j = tid; j < (int64_t)B * W; j += 1024) mb = max(mb, __float_as_uint(fabsf(queries[j])));
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mb = max(mb, (unsigned)__shfl_xor((int)mb, off, 64));
+    mb = wave_max(mb);
     if ((tid & 63) == 0 && mb) atomicMax(&s_max, mb);
     __syncthreads();
     const unsigned qmaxbits = s_max;
@@ -1355,8 +1352,7 @@ __global__ __launch_bounds__(PSH_MQ_THREADS) void boot_mq_kernel(ScanArgs a) {
                 float m = __uint_as_float(PSH_INF_BITS);
 #pragma unroll
                 for (int i = 0; i < PSH_L; ++i) m = (i < nvalid) ? fminf(m, acc[i]) : m;
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) m = fminf(m, __shfl_xor(m, off, 64));
+                m = wave_min(m);
                 if (lane == 0) a.minbuf[(int64_t)(q0 + ql) * a.min_stride + (int64_t)u] = m;
             }
         }
@@ -1364,8 +1360,7 @@ __global__ __launch_bounds__(PSH_MQ_THREADS) void boot_mq_kernel(ScanArgs a) {
         u = un;
     }
     if (a.blockmax) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) wmax = fmaxf(wmax, __shfl_xor(wmax, off, 64));
+        wmax = wave_max(wmax);
         if (lane == 0) atomicMax(reinterpret_cast<unsigned*>(next_unit + 1), __float_as_uint(wmax));
         __syncthreads();
         if (threadIdx.x == 0) a.blockmax[blockIdx.y * gridDim.x + blockIdx.x] = __uint_as_float((unsigned)next_unit[1]);

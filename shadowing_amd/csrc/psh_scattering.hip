@@ -63,16 +63,11 @@
 #include "psh_kernels.h"
 #include "psh_mrw_lds.h"    // mrw_slot, cmul, mrw_butterfly (through mrw_passes): the forward transform
 #include "psh_scat_lds.h"   // scat_inverse: its counterpart
+#include "psh_wave.h"
 
 namespace psh {
 
 namespace {
-
-__device__ __forceinline__ double scat_wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = v + __shfl_xor(v, d);
-    return v;
-}
 
 // the rows per unit of a group of c rows
 __device__ __forceinline__ int64_t scat_rows_per_unit(int64_t c) { return (c + 15) / 16; }
@@ -142,20 +137,12 @@ __global__ __launch_bounds__(PSH_SCAT_THREADS) void scat_kernel(ScatArgs a) {
                 s2 = s2 + u * u;
                 buf[mrw_slot(t)] = make_double2(u, 0.0);
             }
-            s1 = scat_wave_sum(s1);
-            s2 = scat_wave_sum(s2);
-            if (lane == 0) {
-                red[wave] = s1;
-                red[PSH_SCAT_WAVES + wave] = s2;
-            }
+            block_reduce_put(s1, red, WaveSum{});
+            block_reduce_put(s2, red + PSH_SCAT_WAVES, WaveSum{});
             __syncthreads();
             if (tid == 0) {
-                double t1 = red[0], t2 = red[PSH_SCAT_WAVES];
-#pragma unroll
-                for (int w = 1; w < PSH_SCAT_WAVES; ++w) {
-                    t1 = t1 + red[w];
-                    t2 = t2 + red[PSH_SCAT_WAVES + w];
-                }
+                const double t1 = block_reduce_fold<PSH_SCAT_WAVES>(red, WaveSum{});
+                const double t2 = block_reduce_fold<PSH_SCAT_WAVES>(red + PSH_SCAT_WAVES, WaveSum{});
                 acc[j - 1] = acc[j - 1] + t1 * inv_n;             // the means over t (1 / n: exact)
                 acc[J + j - 1] = acc[J + j - 1] + t2 * inv_n;
             }
@@ -183,8 +170,8 @@ __global__ __launch_bounds__(PSH_SCAT_THREADS) void scat_kernel(ScatArgs a) {
                         re = re + w2 * (u.x * v.x + u.y * v.y);           // u conj(v)
                         im = im + w2 * (u.y * v.x - u.x * v.y);
                     }
-                    re = scat_wave_sum(re);
-                    im = scat_wave_sum(im);
+                    re = wave_sum(re);
+                    im = wave_sum(im);
                     if (lane == 0) {
                         if (jp < j) {
                             const int p3 = j2 * (j2 - 1) / 2 + (j - 1);

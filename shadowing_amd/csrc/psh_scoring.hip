@@ -43,7 +43,7 @@
 //   * LDS: the scans' scratch is the quantiles' (9 KiB at 1024 threads); the tree adds 5 doubles a wave, 640 bytes.  The
 //     16384-entry instantiation holds 148936 bytes of the 163840 a workgroup may hold.
 //   * Small grids: with fewer columns than compute units, a second grid dimension splits the sets into groups, each group
-//     sorting again, as many groups as fill PSH_SCORE_CUS = 256 units.  Each set is computed by the same code from the same
+//     sorting again, as many groups as fill PSH_SMALL_GRID_CUS = 256 units.  Each set is computed by the same code from the same
 //     sorted order, so the bits do not depend on the split.
 //
 // Measured on MI355X (tools/bench_scoring.py: median ms of 20 calls, three alternating rounds, every case in one process,
@@ -75,10 +75,10 @@ namespace psh {
 
 namespace {
 
-#define PSH_SCORE_CUS 256       // compute units a small grid is spread over
-
 // Sums of v[0..2] and maxima (of values >= 0) of v[3..4] over the workgroup, in a fixed tree: a butterfly over a wave's 64
-// lanes, then the waves in order.  Every thread returns with the same five numbers.
+// lanes, then the waves in order.  Every thread returns with the same five numbers.  (The tree of psh_wave.h's block_reduce,
+// written out: the five butterflies go step by step here, their shuffles overlapping; as five wave_reduce in a row the
+// 1024-thread kernel measured 0.7 % slower at 64 x 8192 x 3 with 16 sets.)
 template <int WAVES>
 __device__ __forceinline__ void score_reduce(double (*red)[WAVES], double* v, int tid) {
 #pragma unroll
@@ -232,7 +232,7 @@ hipError_t launch_score(const ScoreArgs& args, hipStream_t s) {
     ScoreArgs a = args;
     const int64_t cols = (int64_t)a.B * a.m;
     int groups = 1;                                           // groups of sets, each sorting again, while units stand idle
-    if (cols < PSH_SCORE_CUS) groups = (int)(PSH_SCORE_CUS / cols) < a.n_sets ? (int)(PSH_SCORE_CUS / cols) : a.n_sets;
+    if (cols < PSH_SMALL_GRID_CUS) groups = (int)(PSH_SMALL_GRID_CUS / cols) < a.n_sets ? (int)(PSH_SMALL_GRID_CUS / cols) : a.n_sets;
     a.sets_per_group = (a.n_sets + groups - 1) / groups;
     const dim3 grid((unsigned)cols, (unsigned)((a.n_sets + a.sets_per_group - 1) / a.sets_per_group));
     if (a.k <= 1024) hipLaunchKernelGGL((score_kernel<1024, 256, 2>), grid, dim3(256), 0, s, a);

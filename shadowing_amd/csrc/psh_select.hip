@@ -44,12 +44,7 @@ __device__ inline void block_minmax64(WalkFn walk, SelectShared* sm, uint64_t* o
         lo = k < lo ? k : lo;
         hi = k > hi ? k : hi;
     });
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint64_t l2 = __shfl_xor(lo, off, 64), h2 = __shfl_xor(hi, off, 64);
-        lo = l2 < lo ? l2 : lo;
-        hi = h2 > hi ? h2 : hi;
-    }
+    wave_minmax(lo, hi);
     if ((tid & 63) == 0) { atomicMin((unsigned long long*)&sm->kmin, (unsigned long long)lo); atomicMax((unsigned long long*)&sm->kmax, (unsigned long long)hi); }
     __syncthreads();
     *out_min = sm->kmin;
@@ -114,40 +109,18 @@ __device__ inline void radix_select64_walk(WalkFn walk, int rank, int sh_floor,
             // (a serial walk by one thread is NB dependent LDS round trips)
             constexpr int PER = (int)(NB / 64);
             const int rem = sm->remaining;
-            unsigned h[PER];
-            unsigned sl = 0;
-#pragma unroll
-            for (int q = 0; q < PER; ++q) { h[q] = sm->hist[PER * tid + q]; sl += h[q]; }
-            unsigned inc = sl;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const unsigned v = __shfl_up(inc, off, 64);
-                if (tid >= off) inc += v;
+            const RankHist<PER> rh(sm->hist, tid);
+            if (first && rank_b > 0) {                              // the second rank's bucket
+                rh.find((unsigned)rank_b, [&](const RankBucket& rb) {
+                    sm->prefix_b = prefix | ((uint64_t)(unsigned)rb.bucket << sh) | ((sh > 0) ? ((1ull << sh) - 1ull) : 0ull);   // upper edge
+                });
             }
-            unsigned cum = inc - sl;
-            if (first && rank_b > 0 && cum < (unsigned)rank_b && inc >= (unsigned)rank_b) {   // the second rank's bucket
-                unsigned c2 = cum;
-                int bucket_b = PER * tid;
-#pragma unroll
-                for (int q = 0; q < PER; ++q) {
-                    if (c2 < (unsigned)rank_b && c2 + h[q] >= (unsigned)rank_b) bucket_b = PER * tid + q;
-                    c2 += h[q];
-                }
-                sm->prefix_b = prefix | ((uint64_t)(unsigned)bucket_b << sh) | ((sh > 0) ? ((1ull << sh) - 1ull) : 0ull);   // upper edge
-            }
-            if (cum < (unsigned)rem && inc >= (unsigned)rem) {      // exactly one lane
-                int bucket = PER * tid;
-                unsigned before = cum, hb = 0;
-#pragma unroll
-                for (int q = 0; q < PER; ++q) {
-                    if (cum < (unsigned)rem && cum + h[q] >= (unsigned)rem) { bucket = PER * tid + q; before = cum; hb = h[q]; }
-                    cum += h[q];
-                }
-                const int r2 = rem - (int)before;
+            rh.find((unsigned)rem, [&](const RankBucket& rb) {
+                const int r2 = rem - (int)rb.before;
                 sm->remaining = r2;
-                sm->prefix = prefix | ((uint64_t)(unsigned)bucket << sh);
-                sm->done = ((int)hb == r2) ? 1 : 0;
-            }
+                sm->prefix = prefix | ((uint64_t)(unsigned)rb.bucket << sh);
+                sm->done = ((int)rb.count == r2) ? 1 : 0;
+            });
         }
         __syncthreads();
         sh_done = sh;
@@ -231,12 +204,7 @@ __global__ __launch_bounds__(PSH_SELECT_THREADS, 8) void threshold_kernel(Thresh
             kmin32 = kb < kmin32 ? kb : kmin32;
             kmax32 = kb > kmax32 ? kb : kmax32;
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const unsigned l2 = __shfl_xor(kmin32, off, 64), h2 = __shfl_xor(kmax32, off, 64);
-            kmin32 = l2 < kmin32 ? l2 : kmin32;
-            kmax32 = h2 > kmax32 ? h2 : kmax32;
-        }
+        wave_minmax(kmin32, kmax32);
         if ((tid & 63) == 0) {
             atomicMin((unsigned long long*)&sm.kmin, (unsigned long long)kmin32 << 32);
             atomicMax((unsigned long long*)&sm.kmax, (unsigned long long)kmax32 << 32);
@@ -493,13 +461,7 @@ __global__ __launch_bounds__(PSH_SELECT_THREADS) void rank_select_kernel(SelectA
                 c2[e] = cf < a.slice ? cf : a.slice;
             }
         }
-        int v = c2[0] + c2[1];
-        v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);         // inclusive scan over the wave
-        v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);
-        v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);
-        v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);
-        v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, true);
-        v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, true);
+        const int v = wave_scan_inclusive_dpp(c2[0] + c2[1]);
         if (lane == 63) sm.wtot[tid >> 6] = v;
         __syncthreads();
         int before = 0;
@@ -582,14 +544,7 @@ __global__ __launch_bounds__(PSH_SELECT_THREADS) void rank_select_kernel(SelectA
             }
 #pragma unroll
             for (int jj = 0; jj < 8; jj += 2) {
-                int v = c[jj] | (c[jj + 1] << 16);                // <= 8 per lane and counter: 512 per wave
-                v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);     // row_shr 1, 2, 4, 8; row_bcast 15, 31
-                v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);
-                v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);
-                v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);
-                v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, true);
-                v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, true);
-                v = __builtin_amdgcn_readlane(v, 63);
+                const int v = wave_total_dpp(c[jj] | (c[jj + 1] << 16));   // <= 8 per lane and counter: 512 per wave
                 if (lane == 0) {
                     if (j0 + jj < nown && (v & 0xffff)) atomicAdd(&sm.rankc[j0 + jj], v & 0xffff);
                     if (j0 + jj + 1 < nown && (v >> 16)) atomicAdd(&sm.rankc[j0 + jj + 1], v >> 16);
@@ -756,12 +711,7 @@ __global__ __launch_bounds__(PSH_SELECT_THREADS, 8) void select_kernel(SelectArg
         if (slices) {      // block min / max of the staged keys
             if (tid == 0) { sm.kmin = ~0ull; sm.kmax = 0ull; }
             __syncthreads();
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const unsigned l2 = __shfl_xor(kmin32, off, 64), h2 = __shfl_xor(kmax32, off, 64);
-                kmin32 = l2 < kmin32 ? l2 : kmin32;
-                kmax32 = h2 > kmax32 ? h2 : kmax32;
-            }
+            wave_minmax(kmin32, kmax32);
             if ((tid & 63) == 0) {
                 atomicMin((unsigned long long*)&sm.kmin, (unsigned long long)kmin32 << 32);
                 atomicMax((unsigned long long*)&sm.kmax, (unsigned long long)kmax32 << 32);

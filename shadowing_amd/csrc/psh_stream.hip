@@ -149,13 +149,8 @@ __device__ __forceinline__ void stream_sample_finish(const ScanArgs& a, const Fu
                     }
             }
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const unsigned l2 = __shfl_xor(kmin, off, 64), h2 = __shfl_xor(kmax, off, 64);
-            kmin = l2 < kmin ? l2 : kmin;
-            kmax = h2 > kmax ? h2 : kmax;
-            nfin += __shfl_xor(nfin, off, 64);
-        }
+        wave_minmax(kmin, kmax);
+        nfin = wave_sum(nfin);
         unsigned edge = 0u;
         if (hinted) {
             // (a hint that is not a positive finite number fails stream_sexp below: not armed -> PSH_STATUS_RETRY)
@@ -180,33 +175,10 @@ __device__ __forceinline__ void stream_sample_finish(const ScanArgs& a, const Fu
                 }
             }
             wave_lds_fence();
-            constexpr int PER = PSH_STREAM_HIST / 64;
-            unsigned h[PER];
-            unsigned sl = 0;
-#pragma unroll
-            for (int c = 0; c < PER; ++c) { h[c] = hist[PER * lane + c]; sl += h[c]; }
-            unsigned inc = sl;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const unsigned t2 = __shfl_up(inc, off, 64);
-                if (lane >= off) inc += t2;
-            }
-            unsigned cum = inc - sl;
-            const unsigned rk = (unsigned)f.rank;
             unsigned my_edge = 0u;
-            const bool mine = cum < rk && inc >= rk;                     // exactly one lane
-            if (mine) {
-                int bucket = PER * lane;
-#pragma unroll
-                for (int c = 0; c < PER; ++c) {
-                    if (cum < rk && cum + h[c] >= rk) bucket = PER * lane + c;
-                    cum += h[c];
-                }
-                // every minimum in buckets <= `bucket` is at or below the bucket's upper edge, and there are >= rank of them
-                u64 e2 = (u64)kmin + (((u64)bucket + 1ull) << shift) - 1ull;
-                if (e2 > (u64)kmax) e2 = kmax;
-                my_edge = (unsigned)e2;
-            }
+            const bool mine = rank_bucket<PSH_STREAM_HIST / 64>(hist, lane, (unsigned)f.rank, [&](const RankBucket& rb) {
+                my_edge = bucket_upper_edge(kmin, kmax, rb.bucket, shift);
+            });
             const u64 who = __ballot(mine);
             edge = (unsigned)__builtin_amdgcn_readlane((int)my_edge, who ? (int)__builtin_ctzll(who) : 0);
         } else {
@@ -218,8 +190,7 @@ __device__ __forceinline__ void stream_sample_finish(const ScanArgs& a, const Fu
             // (stream_sexp with the query's largest |x| taken a lane a sample: a maximum does not depend on the order)
             unsigned mb = 0u;
             for (int j = lane; j < W; j += 64) mb = max(mb, __float_as_uint(fabsf(xs[(size_t)q * W + j])));
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) mb = max(mb, (unsigned)__shfl_xor((int)mb, off, 64));
+            mb = wave_max(mb);
             if (!stream_sexp_of(mb, tau0, &sx)) armed = false;
         } else if (armed && !stream_sexp((const_f32p)a.queries + (size_t)q * W, W, tau0, &sx)) armed = false;   // (uniform: scalar inputs)
         if (lane == 0) { sh_tau0[q] = tau0; sh_sexp[q] = sx; sh_armed[q] = armed ? 1 : 0; }
@@ -251,8 +222,7 @@ __device__ __forceinline__ void stream_sample_finish(const ScanArgs& a, const Fu
             //  where the formula keeps 10^-12 in hand)
             double part = 0.0;
             for (int j = lane; j < W; j += 64) { const double vv = (double)xs[(size_t)q * W + j] * (double)scale; part += vv * vv; }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
+            part = wave_sum(part);
             if (!stream_threshold_of(part, W, tau0q_, scale, &thr, copy)) sh_armed[q] = 0;
         } else if (armed && !stream_threshold(xq, W, tau0q_, scale, &thr, copy)) sh_armed[q] = 0;
         if (copy_flood) thr = __uint_as_float(PSH_INF_BITS);
@@ -346,8 +316,7 @@ void stream_sample_kernel(ScanArgs a, FusedArgs f) {
             float m = __uint_as_float(PSH_INF_BITS);
 #pragma unroll
             for (int i = 0; i < PSH_L; ++i) m = (i < nvalid) ? fminf(m, acc[i]) : m;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) m = fminf(m, __shfl_xor(m, off, 64));
+            m = wave_min(m);
             if (!(m == m)) m = __uint_as_float(PSH_INF_BITS);              // NaN data: the segment carries no information
             if (lane == 0) store_sc1(&hdr->minima[(size_t)q * f.units_stride + u], __float_as_uint(m));   // write-through
         }
@@ -917,8 +886,7 @@ __device__ __forceinline__ void stream_sample_long_body(const ScanArgs& a, const
         const float* xq = xs + (size_t)q * W;
         unsigned mb = 0u;
         for (int j = lane; j < W; j += 64) mb = max(mb, __float_as_uint(fabsf(xq[j])));
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) mb = max(mb, (unsigned)__shfl_xor((int)mb, off, 64));
+        mb = wave_max(mb);
         // (a query with a NaN / inf sample does not bound the scale: its tables hold NaN, its upper bounds come out +inf and the
         //  finish finds fewer finite minima than its rank -> not armed -> PSH_STATUS_RETRY)
         if (lane == 0 && mb >= 0x00800000u && mb < PSH_INF_BITS) atomicMin(&ctlw[0], 3 - ((int)((mb >> 23) & 255u) - 126));
@@ -930,8 +898,7 @@ __device__ __forceinline__ void stream_sample_long_body(const ScanArgs& a, const
         const float* xq = xs + (size_t)q * W;
         double part = 0.0;
         for (int j = lane; j < W; j += 64) { const double vv = (double)xq[j] * (double)scale; part += vv * vv; }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
+        part = wave_sum(part);
         if (lane == 0) nxq[q] = (float)(part * (1.0 + 1e-6));
     }
     for (int e = tid; e < nq * 8 * CP; e += 64 * NWP) {                       // copy c, chunk v, half i: -2 x~[8 (v - 3) + i - c]
@@ -1027,8 +994,7 @@ __device__ __forceinline__ void stream_sample_long_body(const ScanArgs& a, const
                     mn = p < nvalid ? fminf(mn, c[r]) : mn;
                 }
             }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) mn = fminf(mn, __shfl_xor(mn, off, 64));
+            mn = wave_min(mn);
             // An upper bound of the smallest acc of the unit (scan_lq_kernel's BOOT has the derivation):
             //     acc~ (1 - 2 a) <= t^ + nx~ (1 + 3 a) + b,   back to the data's scale.
             // A unit whose estimate t^ + nx~ is below nx~ / 6 -- a near-match: smooth ensembles -- would get a bound made of the
@@ -1063,8 +1029,7 @@ __device__ __forceinline__ void stream_sample_long_body(const ScanArgs& a, const
                 float mq = __uint_as_float(PSH_INF_BITS);
 #pragma unroll
                 for (int i = 0; i < PSH_L; ++i) mq = (i < nv) ? fminf(mq, acc[i]) : mq;
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) mq = fminf(mq, __shfl_xor(mq, off, 64));
+                mq = wave_min(mq);
                 if (!(mq == mq)) mq = __uint_as_float(PSH_INF_BITS);
                 if (lane == 0) store_sc1(&hdr->minima[(size_t)q * f.units_stride + u], __float_as_uint(mq));
             }
@@ -1175,8 +1140,7 @@ void stream_rank_kernel(ScanArgs a, FusedArgs f) {
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) {
             int v = c[jj];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+            v = wave_sum(v);
             rank = lane == jj ? v : rank;
         }
         if (lane < 8 && j0 + lane < hi && rank < a.k) {

@@ -52,12 +52,11 @@
 #include "psh.h"
 #include "psh_kernels.h"
 #include "psh_sort_lds.h"
+#include "psh_wave.h"
 
 namespace psh {
 
 namespace {
-
-#define PSH_WGT_CUS 256         // compute units a small grid is spread over
 
 // qnt_key with every NaN behind +inf
 __device__ __forceinline__ uint32_t wgt_key(float x) { return x != x ? 0xffffffffu : qnt_key(x); }
@@ -123,12 +122,9 @@ __global__ __launch_bounds__(THREADS) void weights_kernel(WeightsArgs a) {
             has_nan |= (kept && zz != zz) ? 1 : 0;
             m = kept ? fmax(m, zz) : m;                   // (fmax drops a NaN: the flag carries it)
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
-        if ((tid & 63) == 0) red[0][tid >> 6] = m;
-        has_nan = __syncthreads_or(has_nan);
-        double zmax = red[0][0];
-        for (int u = 1; u < WAVES; ++u) zmax = fmax(zmax, red[0][u]);
+        block_reduce_put(m, red[0], WaveMax{});
+        has_nan = __syncthreads_or(has_nan);              // (the tree's barrier, carrying the flag)
+        double zmax = block_reduce_fold<WAVES>(red[0], WaveMax{});
         if (has_nan) zmax = qnan;
 
         // ---- e = exp(z - zmax); Z
@@ -141,12 +137,7 @@ __global__ __launch_bounds__(THREADS) void weights_kernel(WeightsArgs a) {
             z[i] = ev;
             sum = tid + i * THREADS < kc ? sum + ev : sum;
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) sum = sum + __shfl_xor(sum, o);
-        if ((tid & 63) == 0) red[1][tid >> 6] = sum;
-        __syncthreads();
-        double Z = red[1][0];
-        for (int u = 1; u < WAVES; ++u) Z = Z + red[1][u];
+        const double Z = block_reduce<WAVES>(sum, red[1], WaveSum{});
 
         // ---- w at the path's own index
 #pragma unroll
@@ -163,7 +154,7 @@ hipError_t launch_softmax_weights(const WeightsArgs& args, hipStream_t s) {
     WeightsArgs a = args;
     const int n_sets = a.n_etas * a.n_ks;
     int groups = 1;                                           // groups of sets, each sorting again, while units stand idle
-    if (a.B < PSH_WGT_CUS) groups = PSH_WGT_CUS / a.B < n_sets ? PSH_WGT_CUS / a.B : n_sets;
+    if (a.B < PSH_SMALL_GRID_CUS) groups = PSH_SMALL_GRID_CUS / a.B < n_sets ? PSH_SMALL_GRID_CUS / a.B : n_sets;
     a.sets_per_group = (n_sets + groups - 1) / groups;
     const dim3 grid((unsigned)a.B, (unsigned)((n_sets + a.sets_per_group - 1) / a.sets_per_group));
     if (a.k <= 1024) hipLaunchKernelGGL((weights_kernel<1024, 256, 2>), grid, dim3(256), 0, s, a);
