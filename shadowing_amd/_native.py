@@ -282,9 +282,26 @@ class FilterCopy:
         self._built = False                  # the event has been seen complete: nobody waits any more
         self.desc = PshFilterCopy(self.buf.data_ptr(), pitch, R, T, 0, 0)
 
+    def wait(self) -> None:
+        """Block the host until the build has completed and remember that it has: from then on use() issues no event call on
+        any stream.  Call it (outside a capture) before a scan that reads the copy is captured into a graph."""
+        if not self._built:
+            self.event.synchronize()
+            self._built = True
+
     def use(self, stream: "torch.cuda.Stream") -> None:
-        """Call before enqueueing a scan that reads the copy on `stream`."""
+        """Call before enqueueing a scan that reads the copy on `stream`.  While `stream` captures a graph nothing is asked
+        of the event or the allocator (an event query is illegal then, and the graph is replayed on other streams anyway): a
+        copy seen complete -- wait() -- or captured on its builder's stream is used as it is, any other raises here, before
+        anything reaches HIP.  Whoever replays the graph keeps the copy alive and current as long as the graph."""
         sp = stream.cuda_stream
+        if sp in self._streams and (self._built or sp == self._builder):
+            return
+        if _filter_copy_capturing():
+            if not self._built and sp != self._builder:
+                raise NativeLibraryError("a FilterCopy whose build has not been seen complete cannot be used while the stream "
+                                         "captures a graph: call its wait() before the capture begins")
+            return
         if sp not in self._streams:
             self.buf.record_stream(stream)
             self._streams.add(sp)
@@ -324,13 +341,14 @@ def _filter_copy_auto(ds: torch.Tensor):
     """The "auto" policy: the FilterCopy that serves this call, or None.  One entry per base tensor (it dies with the
     tensor); a call whose key -- data pointer, shape, strides, device, version counter -- differs from the entry's starts over.
     The copy is built on the second consecutive eligible call with one key ("second"; "first": at once), if the device has
-    room for it and 1 GiB more, and never while the stream is capturing."""
+    room for it and 1 GiB more, and never while the stream is capturing.  Nor is an existing copy SERVED to a capturing stream:
+    the version counter is read now, the graph is replayed later, on an ensemble its owner may have refreshed in place since."""
     import weakref
     base, key = _filter_copy_key(ds)
     ent = _filter_copies.get(id(base))
     if ent is not None and ent["ref"]() is base and ent["key"] == key:
         if ent["copy"] is not None:
-            return ent["copy"]
+            return None if _filter_copy_capturing() else ent["copy"]
         ent["calls"] += 1
     else:
         bid = id(base)
@@ -430,7 +448,8 @@ def scan_topk(dataset: torch.Tensor, queries: torch.Tensor, k: int, h: int = 0, 
     `filter_copy`: a FilterCopy of `dataset`, None, or "auto" (default) -- the one-query overlap scan (B = 1, W <= 33,
     FLAG_OVERLAP) streams a resident f16 copy of the ensemble, built on the second consecutive such call on the same
     unchanged tensor (FILTER_COPY_POLICY, PSH_FILTER_COPY=0, filter_copy_forget; INTEGRATION.md).  Results do not depend on it;
-    `info` receives `copy_served` / `copy_reason`.
+    `info` receives `copy_served` / `copy_reason`.  While the stream captures a graph "auto" neither builds nor serves a copy
+    (a replay may meet an ensemble edited since); a FilterCopy passed in is served, its staleness being the caller's business.
     """
     ds = _dev_tensor(dataset, torch.float32, "dataset")
     q = _dev_tensor(queries, torch.float32, "queries")

@@ -127,3 +127,88 @@ def test_nothing_is_built_while_the_stream_captures(policy):
     assert auto(ds) is None and auto(ds) is None and auto(ds) is None and not built
     state["capturing"] = False
     assert auto(ds) is built[0]                            # the calls were counted: the first one outside a capture builds
+
+
+def test_nothing_is_served_while_the_stream_captures(policy):
+    """A graph is replayed after the capture-time look at the version counter: an entry that exists is not handed to a
+    capturing stream, and is there again once the capture is over (nothing was dropped, nothing rebuilt)."""
+    built, state = policy
+    ds = torch.zeros(64, 2048)
+    auto(ds)
+    c = auto(ds)
+    assert c is built[0]
+    state["capturing"] = True
+    assert auto(ds) is None and auto(ds) is None and len(built) == 1
+    state["capturing"] = False
+    assert auto(ds) is c and len(built) == 1
+
+
+class FakeEvent:
+    def __init__(self, done):
+        self.done, self.calls = done, []
+
+    def query(self):
+        self.calls.append("query")
+        return self.done
+
+    def synchronize(self):
+        self.calls.append("synchronize")
+        self.done = True
+
+
+class FakeBuf:
+    def __init__(self):
+        self.recorded = []
+
+    def record_stream(self, stream):
+        self.recorded.append(stream.cuda_stream)
+
+
+class FakeStream:
+    def __init__(self, ptr):
+        self.cuda_stream, self.waits = ptr, []
+
+    def wait_event(self, ev):
+        self.waits.append(ev)
+
+
+def _copy(done, builder=1):
+    """A FilterCopy as its constructor leaves it, without a device: built on stream `builder`, event complete or not."""
+    c = object.__new__(_native.FilterCopy)
+    c.event, c.buf, c._builder, c._streams, c._built = FakeEvent(done), FakeBuf(), builder, {builder}, False
+    return c
+
+
+def test_use_makes_no_event_or_allocator_call_while_the_stream_captures(policy):
+    _, state = policy
+    # outside a capture: a new stream is made known to the allocator and asks the event (complete: remembered; not: waits)
+    c, s2 = _copy(True), FakeStream(2)
+    c.use(s2)
+    assert c.event.calls == ["query"] and c.buf.recorded == [2] and c._built and not s2.waits
+    c, s2 = _copy(False), FakeStream(2)
+    c.use(s2)
+    assert c.event.calls == ["query"] and s2.waits == [c.event] and not c._built
+    # capturing, the build not seen complete: a Python error before any call, and nothing has changed
+    state["capturing"] = True
+    c, s3 = _copy(True), FakeStream(3)
+    with pytest.raises(_native.NativeLibraryError, match=r"wait\(\)"):
+        c.use(s3)
+    assert c.event.calls == [] and c.buf.recorded == [] and not s3.waits and c._streams == {1}
+    # ... seen complete (wait(), outside the capture): used as it is, on any stream, without a call
+    state["capturing"] = False
+    c.wait()
+    assert c.event.calls == ["synchronize"] and c._built
+    state["capturing"] = True
+    c.use(s3)
+    c.use(FakeStream(1))
+    assert c.event.calls == ["synchronize"] and c.buf.recorded == [] and not s3.waits
+    # ... and a capture on the builder's own stream is in stream order behind the build
+    c = _copy(False)
+    c.use(FakeStream(1))
+    assert c.event.calls == [] and c.buf.recorded == []
+    # after the capture the new stream registers as ever
+    state["capturing"] = False
+    c, s3 = _copy(True), FakeStream(3)
+    c.wait()
+    c.use(s3)
+    assert c.buf.recorded == [3] and c.event.calls == ["synchronize"]
