@@ -366,7 +366,6 @@ hipError_t launch_copy_scan(const ScanArgs& a, const FusedArgs& f, const CopyArg
 __host__ __device__ inline int lq_ksteps(int W) { return (W + 31 + 15) / 16; }
 // the K-steps are compiled in as 6 / 10 / 14 / 18 (a band that ends earlier multiplies zero tables)
 __host__ __device__ inline int lq_bucket(int W) { const int n = lq_ksteps(W); return n <= 6 ? 6 : (n <= 10 ? 10 : (n <= 14 ? 14 : 18)); }
-__host__ __device__ constexpr int lq_rows(int nks) { return 31 + (nks + 1) / 2; }
 // A query's B fragments as EIGHT SHIFTED COPIES of -2 x~ (round 6, second form) instead of one fragment per (K-step, lane): the
 // fragment of lane (n = 8 a + c, hk), K-step s is -2 x~[16 s + 8 hk + i - n], i < 8 = the 16-byte chunk 2 s + hk - a + 3 of copy
 // c, where copy c holds Z_c[m] = -2 x~[m - 24 - c] (zero outside the window): an ALIGNED 16-byte read at a per-lane base plus

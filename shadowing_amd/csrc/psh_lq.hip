@@ -21,23 +21,19 @@
 // Results are the exact top-k: what is ranked is always the sequential fp32 chain (include/psh.h).
 #include <type_traits>
 #include "psh_launch.h"
-#include "psh_segment.h"
+#include "psh_long.h"
 
 namespace psh {
 
 
 #define PSH_LQ_THREADS 512
-#define PSH_LQ_ROW 40                 // halves a row of 32 samples takes (8 of padding: ds_read_b128 of 16 rows on 16 bank quads)
-#define PSH_LQ_SFLOATS 1280           // prefix sums of a segment's squares: entries 0 .. SEG + W - 1 <= 1279
-#define PSH_LQ_QCAP 64                // deferred survivors a wave keeps
-#define PSH_LQ_GAMMA 7.62939453125e-06f   // 2^-17 (psh_stream.hip, PSH_LONG_GAMMA: the same construction, the same bound)
 #define PSH_LQ_FIXED 2048             // control words, per-query constants and counters
 #define PSH_LQ_MAXQ 32                // queries a chunk holds at most
 
-// (lq_ksteps, lq_bucket, lq_rows, lq_copy_chunks, lq_query_bytes: psh_kernels.h -- the long-window sample of the three launches,
-//  psh_stream.hip, lays its tables out the same way)
+// (lq_ksteps, lq_bucket, lq_copy_chunks, lq_query_bytes: psh_kernels.h -- the long-window sample of the three launches,
+//  psh_stream.hip, lays its tables out the same way; the rows, the prefix sums and the queue: psh_long.h)
 __host__ __device__ inline size_t lq_wave_bytes(int nks) {
-    return (size_t)PSH_LQ_SFLOATS * 4 + (size_t)PSH_LQ_QCAP * 8 + (size_t)lq_rows(nks) * PSH_LQ_ROW * 2;
+    return (size_t)PSH_LONG_SFLOATS * 4 + (size_t)PSH_LONG_QCAP * 8 + (size_t)long_nhalf(nks) * 2;
 }
 
 // MODE: PSH_MODE_BOOT / PSH_MODE_FILTER.  NKS: K-steps compiled in.
@@ -59,30 +55,18 @@ __global__ __launch_bounds__(PSH_LQ_THREADS) void scan_lq_kernel(ScanArgs a) {
     constexpr int CP = lq_copy_chunks(NKS), QS = lq_query_bytes(NKS) / 2;     // chunks a copy, HALVES a query
     char* wbase = reinterpret_cast<char*>(tab + (size_t)a.q_per_group * QS) + (size_t)wave * lq_wave_bytes(NKS);
     float* sp = reinterpret_cast<float*>(wbase);                              // prefix sums
-    unsigned* sq_row = reinterpret_cast<unsigned*>(sp + PSH_LQ_SFLOATS);      // deferred survivors: row, t | query << 27
-    unsigned* sq_tq = sq_row + PSH_LQ_QCAP;
-    _Float16* a1 = reinterpret_cast<_Float16*>(sq_tq + PSH_LQ_QCAP);          // rows of {y^ [32], pad [8]}
+    unsigned* sq_row = reinterpret_cast<unsigned*>(sp + PSH_LONG_SFLOATS);    // deferred survivors: row, t | query << 27
+    unsigned* sq_tq = sq_row + PSH_LONG_QCAP;
+    _Float16* a1 = reinterpret_cast<_Float16*>(sq_tq + PSH_LONG_QCAP);        // rows of {y^ [32], pad [8]}
 
     const int nfloat = PSH_SEG + W - 1;
     const UnitQueue uq = unit_queue((unsigned)a.n_rows * (unsigned)a.nseg, &ctl[1]);
-    const int lane16 = lane * 16;
     // (two units in flight per wave -- a second Stage, the loop body twice -- moved the kernel's floor at W = 64 from 1.33 to 1.02 ms
     //  and nothing at W >= 126, where the floor is the per-segment work, not the loaded latency: not kept)
     Stage st;
-    auto stage_row = [&](Stage& st, int64_t row, int seg_start) {
-        const int64_t bytes = a.T * 4;
-        const __amdgpu_buffer_rsrc_t rs = buffer_rsrc(a.dataset + row * a.T, (unsigned)(bytes > 0x7ffffffc ? 0x7ffffffc : bytes));
-        const int nq4 = (nfloat + 3) >> 2;
-#pragma unroll
-        for (int q = 0; q < PSH_NSTAGE; ++q)
-            if (q < PSH_NSTAGE - 1 || lane + 64 * q < nq4) {
-                const u32x4v w = __builtin_amdgcn_raw_buffer_load_b128(rs, lane16 + 1024 * q, seg_start * 4, 0);
-                st.v[q] = f32x4{__uint_as_float(w[0]), __uint_as_float(w[1]), __uint_as_float(w[2]), __uint_as_float(w[3])};
-            }
-    };
     auto load_unit = [&](Stage& sx, unsigned uu) {
         const Unit c = unit_decode(a, uu);
-        stage_row(sx, c.row(a), c.seg_start());
+        long_stage_row<0>(sx, a.dataset, a.T, c.row(a), c.seg_start(), nfloat, lane);
     };
     unsigned u = uq.lo + (unsigned)wave;
     if (u < uq.hi) load_unit(st, u);
@@ -147,30 +131,13 @@ __global__ __launch_bounds__(PSH_LQ_THREADS) void scan_lq_kernel(ScanArgs a) {
         }
         qc[4 * tid + 0] = out;
     }
-    // the tables: copy c, chunk v, half i holds -2 x~[8 (v - 3) + i - c]; zero outside the window
-    for (int e = tid; e < nq * 8 * CP; e += PSH_LQ_THREADS) {
-        const int v = e % CP, c = (e / CP) & 7, ql = e / (8 * CP);
-        const float* xq = xs + (size_t)ql * W;
-        f16x8 b;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int j = 8 * (v - 3) + i - c;
-            const bool in = j >= 0 && j < W;
-            const float xv = xq[in ? j : 0];
-            b[i] = (_Float16)(in ? -2.0f * (xv * scale) : 0.0f);
-        }
-        *reinterpret_cast<f16x8*>(tab + (size_t)ql * QS + ((size_t)c * CP + v) * 8) = b;
-    }
+    long_query_tables<NKS>(tab, xs, nq, W, scale, tid, PSH_LQ_THREADS);
     __syncthreads();                                                          // (the staged queries are dead: the waves' buffers)
-    {   // every slot of the rows a segment does not write must be finite (0 * NaN poisons a row)
-        unsigned* z = reinterpret_cast<unsigned*>(a1);
-        for (int i = lane; i < lq_rows(NKS) * PSH_LQ_ROW / 2; i += 64) z[i] = 0u;
-    }
+    long_zero_rows(a1, long_nhalf(NKS) / 2, lane);
     wave_lds_fence();
 
     // ---- deferred survivors (stream_scan_long_kernel's scheme): verified a lane a window, straight from memory
     int qn = 0;
-    typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
     auto verify_queue = [&]() {
 #ifdef PSH_TUNING
         if ((a.dbg & 16) && lane == 0) atomicAdd(&a.bcount[PSH_MAX_BLOCKS - 1], qn);   // probe: survivors verified (tools/lq_ablate.py)
@@ -186,17 +153,7 @@ __global__ __launch_bounds__(PSH_LQ_THREADS) void scan_lq_kernel(ScanArgs a) {
         const float* y = a.dataset + (int64_t)row * a.T + t;
         const float* x = a.queries + (size_t)b * W;
         float v = 0.0f;
-        if (have) {
-            int j = 0;
-#pragma unroll 2
-            for (; j + 4 <= W; j += 4) {
-                const f32x4u yy = *reinterpret_cast<const f32x4u*>(y + j);
-                const f32x4u xx = *reinterpret_cast<const f32x4u*>(x + j);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) { const float D = __fsub_rn(xx[c], yy[c]); v = __builtin_fmaf(D, D, v); }
-            }
-            for (; j < W; ++j) { const float D = __fsub_rn(x[j], y[j]); v = __builtin_fmaf(D, D, v); }
-        }
+        if (have) v = long_exact_window(y, x, W);
         const bool hit = have && (v < qc[4 * ql + 1]);
         if (hit) {
             const int pos = atomicAdd(&lcount[ql], 1);
@@ -211,7 +168,7 @@ __global__ __launch_bounds__(PSH_LQ_THREADS) void scan_lq_kernel(ScanArgs a) {
     };
 
     const int m = lane & 31, hk = lane >> 5;
-    const _Float16* pa0 = a1 + m * PSH_LQ_ROW + 8 * hk;
+    const _Float16* pa0 = a1 + m * PSH_LONG_ROW + 8 * hk;
     const _Float16* pb0 = tab + ((size_t)(m & 7) * CP + (hk - (m >> 3) + 3)) * 8;       // copy n & 7, chunk hk - (n >> 3) + 3 (+ 2 s a K-step)
     const float* ps_lo = sp + m + 128 * hk;
     const float* ps_hi = ps_lo + W;
@@ -230,7 +187,7 @@ __global__ __launch_bounds__(PSH_LQ_THREADS) void scan_lq_kernel(ScanArgs a) {
                 const bool on = q < PSH_NSTAGE - 1 || mm < nq4;
                 const f32x4 v = on ? st.v[q] * scale : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
                 const f32x4 z = v * v;
-                if (on) *reinterpret_cast<f16x4*>(a1 + (mm >> 3) * PSH_LQ_ROW + 4 * (mm & 7)) = __builtin_convertvector(v, f16x4);
+                if (on) *reinterpret_cast<f16x4*>(a1 + (mm >> 3) * PSH_LONG_ROW + 4 * (mm & 7)) = __builtin_convertvector(v, f16x4);
                 d0[q] = z[0]; d1[q] = d0[q] + z[1]; d2[q] = d1[q] + z[2]; d3[q] = d2[q] + z[3];
                 inc[q] = d3[q];
             }
@@ -263,13 +220,9 @@ __global__ __launch_bounds__(PSH_LQ_THREADS) void scan_lq_kernel(ScanArgs a) {
         wave_lds_fence();
         const unsigned un = uq.grab(lane);
         if (un < uq.hi) load_unit(st, un);
-        // the tile's C operand from the prefix sums: FILTER a LOWER bound of the energies (E^ - gamma S), BOOT an UPPER one
-        f32x16 ce;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int off = 32 * (r & 3) + 256 * (r >> 2);
-            ce[r] = __builtin_fmaf(ps_hi[off], MODE == PSH_MODE_FILTER ? 1.0f - PSH_LQ_GAMMA : 1.0f + PSH_LQ_GAMMA, -ps_lo[off]);
-        }
+        // the tile's C operand from the prefix sums: FILTER a LOWER bound of the energies (E^ - gamma S), BOOT an UPPER one;
+        // +inf for the windows the row does not have
+        f32x16 ce = long_energy_operand<MODE != PSH_MODE_FILTER>(ps_lo, ps_hi);
         const int nvalid = a.Tp - seg_start;                                  // windows of this segment that exist (>= 1024: all)
         if (nvalid < PSH_SEG) {
             // A row's last segment: the windows past the last admissible one never pass the test (+inf in their slots of the C
@@ -282,35 +235,18 @@ __global__ __launch_bounds__(PSH_LQ_THREADS) void scan_lq_kernel(ScanArgs a) {
         }
         // BOOT: the minimum of an upper bound of acc per (unit, query)
         auto boot_finish = [&](const f32x16& c, const int ql) __attribute__((always_inline)) {
-            float mn = __uint_as_float(PSH_INF_BITS);
-            if (nvalid >= PSH_SEG) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) mn = fminf(mn, c[r]);
-            } else {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int p = mx_window(r, lane);
-                    mn = p < nvalid ? fminf(mn, c[r]) : mn;
-                }
-            }
-            mn = wave_min(mn);
+            const float mn = long_tile_min(c, nvalid, lane);
             if (lane == 0) {
-                // An upper bound of the smallest acc of the unit, back in the data's scale.  With 2 |c^ - c| <= a (nx~ + E) and
-                // E <= 2 (nx~ + acc~) (stream_threshold's model, read the other way round):
-                //     acc~ (1 - 2 a) <= t^ + nx~ (1 + 3 a) + b.
-                // A unit whose estimate t^ + nx~ is below nx~ / 6 -- a near-match: smooth ensembles -- would get a bound made of the
-                // 3 a nx~ term alone, several times its value; the ESTIMATE (1 + 3 a)(t^ + nx~) stands in there.  Nothing rests on
-                // either being a proof: the level is checked by what it admits (select_kernel: at least k, or the fallback).
+                // An upper bound of the smallest acc of the unit (long_upper_bound).  A unit whose estimate t^ + nx~ is below
+                // nx~ / 6 -- a near-match: smooth ensembles -- would get a bound made of the 3 a nx~ term alone, several times its
+                // value; the ESTIMATE (1 + 3 a)(t^ + nx~) stands in there.  Nothing rests on either being a proof: the level is
+                // checked by what it admits (select_kernel: at least k, or the fallback).
                 const float nx = qc[4 * ql + 0];
                 const float est = fmaxf(mn + nx, 0.0f);
-                const float bb = (float)(2 * W + 2) / 64.0f / 262144.0f;
-                float ub = est < nx * (1.0f / 6.0f)
-                               ? (est * (1.0f + 3.0f / 900.0f + 6.0f * PSH_LQ_GAMMA) + bb) * (1.0f + 1e-6f)
-                               : (est + nx * (3.0f / 900.0f) + bb) * (1.0f + 2.0f / 900.0f + 1.0e-5f + 6.0f * PSH_LQ_GAMMA) * (1.0f + 1e-6f);
-                const float inv = __uint_as_float((unsigned)(127 - sexp) << 23);
-                ub = ub * inv * inv;
-                if (!(ub == ub)) ub = __uint_as_float(PSH_INF_BITS);      // NaN data: the unit carries no information
-                a.minbuf[(int64_t)(q0 + ql) * a.min_stride + (int64_t)u] = ub;
+                a.minbuf[(int64_t)(q0 + ql) * a.min_stride + (int64_t)u] =
+                    est < nx * (1.0f / 6.0f)
+                        ? long_unscale((est * (1.0f + 3.0f / 900.0f + 6.0f * PSH_LONG_GAMMA) + long_bound_b(W)) * (1.0f + 1e-6f), sexp)
+                        : long_upper_bound(est, nx, W, sexp);
             }
         };
         // FILTER, the test of a tile: does it hold a window with t^ <= thr (NaN-safe: !(t^ > thr))?  On a clean segment no NaN can
@@ -356,7 +292,7 @@ __global__ __launch_bounds__(PSH_LQ_THREADS) void scan_lq_kernel(ScanArgs a) {
                 lanes &= lanes - 1ull;
                 unsigned h = (unsigned)__builtin_amdgcn_readlane((int)hm, l);
                 const int n = (int)__popc(h);
-                if (qn + n > PSH_LQ_QCAP) verify_queue();
+                if (qn + n > PSH_LONG_QCAP) verify_queue();
                 if (lane == l) {
                     int slot = qn;
 #pragma unroll 1
@@ -397,7 +333,7 @@ __global__ __launch_bounds__(PSH_LQ_THREADS) void scan_lq_kernel(ScanArgs a) {
 #pragma unroll
             for (int s = 0; s < NKS; ++s) {
                 if (s + 1 < NKS) {
-                    fa[(s + 1) & 1] = ld(pa0 + ((s + 1) >> 1) * PSH_LQ_ROW + 16 * ((s + 1) & 1));
+                    fa[(s + 1) & 1] = ld(pa0 + ((s + 1) >> 1) * PSH_LONG_ROW + 16 * ((s + 1) & 1));
 #pragma unroll
                     for (int j = 0; j < NG; ++j) fb[(s + 1) & 1][j] = ld(pbg + (size_t)j * QS + 16 * (s + 1));
                 }

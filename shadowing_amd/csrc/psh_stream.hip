@@ -27,7 +27,7 @@
 // (scan_mq_kernel: 8 waves per CU, sized for hundreds of queries) streams at half rate.  One f16 scale serves all queries of
 // the step: the largest that every query's proof allows (each query bounds it from above by its own max|x| and tau2).
 #include "psh_launch.h"
-#include "psh_segment.h"
+#include "psh_long.h"
 
 namespace psh {
 
@@ -477,19 +477,8 @@ __device__ __forceinline__ void stream_scan_body(const ScanArgs& a, const FusedA
 // the f16 arrays grow with W and the tables take its place -- so a segment that holds survivors fetches its fp32 values again (one
 // coalesced round trip: the segment was streamed a microsecond ago, L2 / MALL) into the f16 arrays' LDS for the exact chains.  Candidates, status protocol and the launches around it (sample + levels,
 // ranking) are stream_scan_kernel's.
-// The long-window scan's f16 arrays (round 5, second layout): ROWS of 32 samples, a row of y^ followed by the same row of
-// (y~^2)^ and 8 halves of padding -- 72 halves = 144 bytes = 36 dwords a row: the 16 lanes of a ds_read_b128 group (rows m
-// with all 16 residues mod 16, 4 dwords each) fall on 36 m mod 64 = 16 different multiples of 4.  The fragment of row m,
-// K-step s lies at row m + (s >> 1), halves 16 (s & 1) + 8 hk .. + 7 of it: per PAIR of K-steps one pointer moves by one row
-// and every other offset is an immediate -- the slot-rotation layout of the short kernels (mx_half) cost the K-loop 7 vector
-// instructions per step for the address alone, and on this part vector instructions ADD to the matrix cores' time (A.5).
-#define PSH_LONG_ROW 40
-#define PSH_LONG_SFLOATS 1280         // fp32 prefix sums of a segment's squares: entries 0 .. SEG + W - 1 <= 1279; the survivors' scratch afterwards
-#define PSH_LONG_QCAP 64              // deferred survivors a wave keeps before it verifies them (8-byte entries)
-#define PSH_LONG_GAMMA 7.62939453125e-06f   // 2^-17: what the energies' prefix sums may be off by, per unit of the prefix S[p + W] (see below)
-__host__ __device__ inline int stream_long_rows(int W) { return 31 + (stream_ksteps(W) + 1) / 2; }                 // rows the band of row 31 reaches
-__host__ __device__ inline int stream_long_nhalf(int W) { return stream_long_rows(W) * PSH_LONG_ROW; }             // halves per wave (both arrays)
-__device__ __forceinline__ int long_half(int idx) { return (idx >> 5) * PSH_LONG_ROW + (idx & 31); }                // logical sample -> its y^ half ((y~^2)^: + 32)
+// The rows' layout and constants, the staging, the C operand, the zero fill and the exact chain are psh_long.h's, shared with
+// the long-window sample below and scan_lq_kernel (psh_lq.hip); the conversion and its bound are stated here (see there why).
 
 // The band's K-steps of one query: the fragment of K-step s lies at pa0 + (s >> 1) rows + 16 (s & 1) halves, its table at
 // pb + s ts -- every offset an immediate off two registers for all 18 steps a window of 256 takes; one exit.
@@ -520,6 +509,8 @@ done:
 // NQ: one, two or three queries ride one pass (round 5): the window energies' MFMA of a K-step is shared, a query adds one
 // MFMA with its own fragment -- 1 + NQ per step where NQ one-query steps issue 2 NQ -- and the segment is staged and converted
 // once (three queries with W = 126: one pass where the loop of one-query steps made three).
+// (ALIGNED is not used: the buffer loads take any 4-byte aligned row.  It stays in the signature -- the benchmark and the
+//  profile tools name stream_scan_long_kernel<true, NQ>.)
 template <bool ALIGNED, int NQ>
 __device__ __forceinline__ void stream_scan_long_body(const ScanArgs& a, const FusedArgs& f) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -529,7 +520,7 @@ __device__ __forceinline__ void stream_scan_long_body(const ScanArgs& a, const F
     const int tid = (int)threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int W = a.W;
-    const int nks = stream_ksteps(W), nhalf = stream_long_nhalf(W);
+    const int nks = stream_ksteps(W), nhalf = long_nhalf(nks);
     int* ctl = reinterpret_cast<int*>(smem);                                 // 64 control words
     u32x4* fl = reinterpret_cast<u32x4*>(ctl + 64);                           // NFL entries {acc bits, r, t, query}
     _Float16* bxl = reinterpret_cast<_Float16*>(fl + NFL);                    // [K-step][query][lane][8]: -2 x~_q shifted by the lane's column
@@ -543,25 +534,9 @@ __device__ __forceinline__ void stream_scan_long_body(const ScanArgs& a, const F
 
     const int nfloat = PSH_SEG + W - 1;
     const UnitQueue uq = unit_queue((unsigned)a.n_rows * (unsigned)a.nseg, &ctl[S_NEXT]);
-    // A segment is staged by BUFFER loads (round 6): the row is the resource (base = its first float, records = its bytes), a lane's
-    // five 16-byte pieces sit at one constant VGPR offset + immediates, the segment's start is the scalar offset -- no address
-    // arithmetic on the vector ALUs, and what lies beyond the row reads as zero (it only feeds inadmissible windows).  Rows need
-    // 4-byte alignment only: one code path for aligned and unaligned ensembles.
-    const int lane16 = lane * 16;
-    auto stage_row = [&](Stage& sx, int64_t row, int seg_start) {
-        const int64_t bytes = a.T * 4;
-        const __amdgpu_buffer_rsrc_t rs = buffer_rsrc(a.dataset + row * a.T, (unsigned)(bytes > 0x7ffffffc ? 0x7ffffffc : bytes));
-        const int nq4 = (nfloat + 3) >> 2;
-#pragma unroll
-        for (int q = 0; q < PSH_NSTAGE; ++q)
-            if (q < PSH_NSTAGE - 1 || lane + 64 * q < nq4) {
-                const u32x4v w = __builtin_amdgcn_raw_buffer_load_b128(rs, lane16 + 1024 * q, seg_start * 4, 2 /* nt */);
-                sx.v[q] = f32x4{__uint_as_float(w[0]), __uint_as_float(w[1]), __uint_as_float(w[2]), __uint_as_float(w[3])};
-            }
-    };
     auto load_unit = [&](Stage& sx, unsigned uu) {
         const Unit c = unit_decode(a, uu);
-        stage_row(sx, c.row(a), c.seg_start());
+        long_stage_row<2 /* nt */>(sx, a.dataset, a.T, c.row(a), c.seg_start(), nfloat, lane);
     };
     Stage st;
     unsigned u = uq.lo + (unsigned)wave;
@@ -581,10 +556,7 @@ __device__ __forceinline__ void stream_scan_long_body(const ScanArgs& a, const F
         tau2[q] = __uint_as_float(sc->tau2_bits[q]); thr2[q] = __uint_as_float(sc->thr2_bits[q]); xn[q] = __uint_as_float(sc->xn_bits[q]);
     }
     if (tid == 0) { ctl[S_FRONT] = 0; ctl[S_NEXT] = NW; }
-    {   // every slot of the rows a segment does not write must be finite (0 * NaN poisons a row)
-        unsigned* z = reinterpret_cast<unsigned*>(a1);
-        for (int i = lane; i < nhalf / 2; i += 64) z[i] = 0u;
-    }
+    long_zero_rows(a1, nhalf / 2, lane);
     __syncthreads();
     if (armed_w == 0u) return;                                                // uniform: the ranking reports PSH_STATUS_RETRY
     // ---- deferred survivors (round 6).  A window that survives the test goes to the wave's queue -- row, t, query: 8 bytes --
@@ -592,27 +564,15 @@ __device__ __forceinline__ void stream_scan_long_body(const ScanArgs& a, const F
     // whole life on ordinary data, so ONE batch at its end instead of a stall in one segment out of four (re-fetching the segment
     // and running the chains in place was 20 of the scan's 125 us at W = 126).
     int qn = 0;                                                               // entries in the queue (uniform)
-    typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));     // a window starts at any float
     auto verify_queue = [&]() {
-        // a lane per queued window: its W samples straight from memory, 16 bytes a load (64 scattered requests an instruction,
-        // all of them L2 / MALL hits: the segment was streamed microseconds ago), the chain in the reference's order
-        const bool have = lane < qn;
+        const bool have = lane < qn;                                          // a lane per queued window
         const u64 mine = have ? sq[lane] : 0ull;
         const int q = (int)(mine >> 62);
         const unsigned t = (unsigned)(mine >> 32) & 0x3fffffffu;
         const float* y = a.dataset + (int64_t)(unsigned)mine * a.T + t;
         const const_f32p x = (const_f32p)a.queries + (size_t)(NQ == 1 ? 0 : q) * W;
         float v = 0.0f;
-        if (have) {
-            int j = 0;
-#pragma unroll 2
-            for (; j + 4 <= W; j += 4) {
-                const f32x4u yy = *reinterpret_cast<const f32x4u*>(y + j);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) { const float D = __fsub_rn(x[j + c], yy[c]); v = __builtin_fmaf(D, D, v); }
-            }
-            for (; j < W; ++j) { const float D = __fsub_rn(x[j], y[j]); v = __builtin_fmaf(D, D, v); }
-        }
+        if (have) v = long_exact_window(y, x, W);
         float tq = tau2[0], xq = xn[0];
 #pragma unroll
         for (int qq = 1; qq < NQ; ++qq) { tq = q == qq ? tau2[qq] : tq; xq = q == qq ? xn[qq] : xq; }
@@ -702,13 +662,8 @@ __device__ __forceinline__ void stream_scan_long_body(const ScanArgs& a, const F
 #else
         const int nks_run = nks;
 #endif
-        // the tile's C operand: what the prefix sums say about the 16 windows of this lane, E^(p) - gamma S^[p + W]
-        f32x16 ce;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int off = 32 * (r & 3) + 256 * (r >> 2);
-            ce[r] = __builtin_fmaf(ps_hi[off], 1.0f - PSH_LONG_GAMMA, -ps_lo[off]);
-        }
+        // the tile's C operand: a lower bound of the 16 windows' energies, +inf for the windows the row does not have
+        f32x16 ce = long_energy_operand<false>(ps_lo, ps_hi);
         if (a.Tp - seg_start < PSH_SEG) {
             // A row's last segment: the windows past the last admissible one never pass the test (+inf in their slots of the C
             // operand).  Left alone they often do: what lies beyond the row reads as zero, a window of zeros is at acc = ||x||^2,
@@ -843,11 +798,11 @@ __device__ __forceinline__ void stream_sample_long_body(const ScanArgs& a, const
     const int wave = NWP == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int W = a.W, nq = f.nq;
     constexpr int CP = lq_copy_chunks(NKS), QS = lq_query_bytes(NKS) / 2;     // chunks a copy, HALVES a query
-    constexpr int NROWS = lq_rows(NKS);
+    constexpr int NHALF = long_nhalf(NKS);
     int* ctlw = reinterpret_cast<int*>(smem);                                 // [0]: the step's sample exponent
     float* nxq = smem + 4;                                                    // nx~ (1 + 1e-6) per query
     _Float16* tab = reinterpret_cast<_Float16*>(smem + 16);                   // [query][copy c < 8][chunk < CP][8 halves]
-    float* sp = reinterpret_cast<float*>(tab + (size_t)nq * QS) + (size_t)wave * (PSH_LONG_SFLOATS + NROWS * PSH_LONG_ROW / 2);
+    float* sp = reinterpret_cast<float*>(tab + (size_t)nq * QS) + (size_t)wave * (PSH_LONG_SFLOATS + NHALF / 2);
     _Float16* a1 = reinterpret_cast<_Float16*>(sp + PSH_LONG_SFLOATS);        // rows of {y^ [32], pad [8]}
     FusedHdr* hdr = f.hdr;
     StreamCtl* ctl = &hdr->stream;
@@ -858,19 +813,9 @@ __device__ __forceinline__ void stream_sample_long_body(const ScanArgs& a, const
         if (blockIdx.x == 0 && threadIdx.x == 0) { ctl->armed = 0u; ctl->ovf = 0u; for (int q = 0; q < 4; ++q) ctl->ncand[q] = 0u; }
         return;
     }
-    const int lane16 = lane * 16;
     auto load_unit = [&](Stage& sx, unsigned uu) {
         const Unit c = unit_decode(a, uu);
-        const int64_t row = f.boot_row0 + (int64_t)c.ri * f.boot_row_stride;
-        const int64_t bytes = a.T * 4;
-        const __amdgpu_buffer_rsrc_t rs = buffer_rsrc(a.dataset + row * a.T, (unsigned)(bytes > 0x7ffffffc ? 0x7ffffffc : bytes));
-        const int nq4 = (nfloat + 3) >> 2;
-#pragma unroll
-        for (int q = 0; q < PSH_NSTAGE; ++q)
-            if (q < PSH_NSTAGE - 1 || lane + 64 * q < nq4) {
-                const u32x4v w = __builtin_amdgcn_raw_buffer_load_b128(rs, lane16 + 1024 * q, c.seg_start() * 4, 0);
-                sx.v[q] = f32x4{__uint_as_float(w[0]), __uint_as_float(w[1]), __uint_as_float(w[2]), __uint_as_float(w[3])};
-            }
+        long_stage_row<0>(sx, a.dataset, a.T, f.boot_row0 + (int64_t)c.ri * f.boot_row_stride, c.seg_start(), nfloat, lane);
     };
     Stage st;
     unsigned u = blockIdx.x * NWP + (unsigned)wave;
@@ -901,24 +846,9 @@ __device__ __forceinline__ void stream_sample_long_body(const ScanArgs& a, const
         part = wave_sum(part);
         if (lane == 0) nxq[q] = (float)(part * (1.0 + 1e-6));
     }
-    for (int e = tid; e < nq * 8 * CP; e += 64 * NWP) {                       // copy c, chunk v, half i: -2 x~[8 (v - 3) + i - c]
-        const int v = e % CP, c = (e / CP) & 7, q = e / (8 * CP);
-        const float* xq = xs + (size_t)q * W;
-        f16x8 b;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int j = 8 * (v - 3) + i - c;
-            const bool in = j >= 0 && j < W;
-            const float xv = xq[in ? j : 0];
-            b[i] = (_Float16)(in ? -2.0f * (xv * scale) : 0.0f);
-        }
-        *reinterpret_cast<f16x8*>(tab + (size_t)q * QS + ((size_t)c * CP + v) * 8) = b;
-    }
+    long_query_tables<NKS>(tab, xs, nq, W, scale, tid, 64 * NWP);
     if (NWP > 1) __syncthreads(); else wave_lds_fence();                     // (the staged queries are dead: the first wave's scratch)
-    {   // every slot of the rows a segment does not write must be finite (0 * NaN poisons a row)
-        unsigned* z = reinterpret_cast<unsigned*>(a1);
-        for (int i = lane; i < NROWS * PSH_LONG_ROW / 2; i += 64) z[i] = 0u;
-    }
+    long_zero_rows(a1, NHALF / 2, lane);
     if (NWP > 1) __syncthreads(); else wave_lds_fence();
 
     const int m = lane & 31, hk = lane >> 5;
@@ -995,18 +925,13 @@ __device__ __forceinline__ void stream_sample_long_body(const ScanArgs& a, const
                 }
             }
             mn = wave_min(mn);
-            // An upper bound of the smallest acc of the unit (scan_lq_kernel's BOOT has the derivation):
-            //     acc~ (1 - 2 a) <= t^ + nx~ (1 + 3 a) + b,   back to the data's scale.
-            // A unit whose estimate t^ + nx~ is below nx~ / 6 -- a near-match: smooth ensembles -- would get a bound made of the
-            // 3 a nx~ term alone: such a unit is sampled with the exact chains below instead.
+            // An upper bound of the smallest acc of the unit (long_upper_bound).  A unit whose estimate t^ + nx~ is below
+            // nx~ / 6 -- a near-match: smooth ensembles -- would get a bound made of the 3 a nx~ term alone: such a unit is
+            // sampled with the exact chains below instead.
             const float nx = nxq[q];
             const float est = fmaxf(mn + nx, 0.0f);
             if (est < nx * (1.0f / 6.0f)) loose = true;                       // (NaN: not loose -- the bound comes out NaN -> +inf)
-            float ub = (est + nx * (3.0f / 900.0f) + (float)(2 * W + 2) / 64.0f / 262144.0f)
-                       * (1.0f + 2.0f / 900.0f + 1.0e-5f + 6.0f * PSH_LONG_GAMMA) * (1.0f + 1e-6f);
-            const float inv = __uint_as_float((unsigned)(127 - sexp) << 23);
-            ub = ub * inv * inv;
-            if (!(ub == ub)) ub = __uint_as_float(PSH_INF_BITS);              // NaN data: the unit carries no information
+            const float ub = long_upper_bound(est, nx, W, sexp);
             if (lane == 0) store_sc1(&hdr->minima[(size_t)q * f.units_stride + u], __float_as_uint(ub));   // write-through
         }
         wave_lds_fence();                                                     // all lanes done with the arrays before they are overwritten
@@ -1034,10 +959,7 @@ __device__ __forceinline__ void stream_sample_long_body(const ScanArgs& a, const
                 if (lane == 0) store_sc1(&hdr->minima[(size_t)q * f.units_stride + u], __float_as_uint(mq));
             }
             wave_lds_fence();
-            {   // (the rows held fp32 samples: every slot a segment does not write must be finite again)
-                unsigned* z = reinterpret_cast<unsigned*>(a1);
-                for (int i = lane; i < NROWS * PSH_LONG_ROW / 2; i += 64) z[i] = 0u;
-            }
+            long_zero_rows(a1, NHALF / 2, lane);                             // (the rows held fp32 samples)
             wave_lds_fence();
         }
         u = un;
@@ -1164,7 +1086,7 @@ size_t stream_scan_long_shmem_bytes(int W, int nq) {
     // control words, the block's list, the queries' fragment tables; per wave: the prefix sums, the survivors' queue, the f16 rows
     return (size_t)PSH_STREAM_FIXED_BYTES + (size_t)(nq == 1 ? PSH_FUSED_FRONT : 2 * PSH_FUSED_FRONT) * 16
            + (size_t)nq * stream_ksteps(W) * 64 * 8 * sizeof(_Float16)
-           + (size_t)(PSH_SCAN_THREADS / 64) * ((size_t)(PSH_LONG_SFLOATS + 2 * PSH_LONG_QCAP) * sizeof(float) + (size_t)stream_long_nhalf(W) * sizeof(_Float16));
+           + (size_t)(PSH_SCAN_THREADS / 64) * ((size_t)(PSH_LONG_SFLOATS + 2 * PSH_LONG_QCAP) * sizeof(float) + (size_t)long_nhalf(stream_ksteps(W)) * sizeof(_Float16));
 }
 size_t stream_sample_shmem_bytes(int tile_floats) {
     const size_t t = (size_t)tile_floats * sizeof(float), h = (size_t)PSH_STREAM_HIST * sizeof(unsigned);
@@ -1184,7 +1106,7 @@ hipError_t launch_stream_sample(const ScanArgs& a, const FusedArgs& f, bool alig
 
 size_t stream_sample_long_shmem_bytes(int W, int nq) {
     const int nks = lq_bucket(W), nwp = nq == 1 ? 1 : 4;
-    return 64 + (size_t)nq * lq_query_bytes(nks) + (size_t)nwp * ((size_t)PSH_LONG_SFLOATS * 4 + (size_t)lq_rows(nks) * PSH_LONG_ROW * 2);
+    return 64 + (size_t)nq * lq_query_bytes(nks) + (size_t)nwp * ((size_t)PSH_LONG_SFLOATS * 4 + (size_t)long_nhalf(nks) * 2);
 }
 // the long-window step's sample (34 <= W <= 256, no hint): one-wave blocks for one query, a quarter as many four-wave blocks for
 // two or three (launch_stream_sample's rule)

@@ -1,6 +1,6 @@
 """The probe library of the shared device primitives -- TEST INFRASTRUCTURE ONLY.
 
-tests/csrc/psh_probe.hip wraps each primitive of psh_wave.h and psh_sort_lds.h (and fast_div, unit_queue) in a thin
+tests/csrc/psh_probe.hip wraps each primitive of psh_wave.h, psh_sort_lds.h and psh_long.h (and fast_div, unit_queue) in a thin
 kernel; this module builds it with the product's flags into tests/csrc/lib/libpsh_probe.so and binds it with ctypes.
 Nothing in shadowing_amd/ imports, links or loads it, and libpsh_hip.so exports none of its symbols
 (tests/test_wave_twin_cpu.py holds both).  The same rules as the product's library: `build()` compiles when the
@@ -23,16 +23,19 @@ from shadowing_amd import _build  # noqa: E402
 SOURCE = HERE / "csrc" / "psh_probe.hip"
 LIBDIR = HERE / "csrc" / "lib"
 LIB = LIBDIR / "libpsh_probe.so"
-# what the probe is built from: its source and the four headers it includes by name (psh_kernels.h comes in through
+# what the probe is built from: its source and the five headers it includes by name (psh_kernels.h comes in through
 # psh_device.h and holds argument blocks only)
-HEADERS = [_build.CSRC / "psh_wave.h", _build.CSRC / "psh_sort_lds.h", _build.CSRC / "psh_device.h", _build.CSRC / "psh_segment.h"]
+HEADERS = [_build.CSRC / "psh_wave.h", _build.CSRC / "psh_sort_lds.h", _build.CSRC / "psh_device.h", _build.CSRC / "psh_segment.h", _build.CSRC / "psh_long.h"]
 DEPS = [SOURCE] + HEADERS
-PROBE_VERSION = 1
+PROBE_VERSION = 2
 
 # wave / block_reduce operand types and operations (the enums of psh_probe.hip)
 F32, F64, I32, U32 = 0, 1, 2, 3
 SUM, MIN, MAX, OR, MINMAX, SCAN = 0, 1, 2, 3, 4, 5
 DPP_MAX_NONNEG, DPP_SUM, DPP_SCAN, DPP_TOTAL = 0, 1, 2, 3
+# psh_probe_long: the piece, and the ints of a case's parameter block
+L_STAGE0, L_STAGE2, L_OPERAND_LO, L_OPERAND_HI, L_TILE_MIN, L_TABLES, L_EXACT_SCALAR, L_EXACT_VECTOR, L_BOUND, L_ZERO = range(10)
+LONG_PARAMS = 136
 
 
 class ProbeLibraryError(RuntimeError):
@@ -53,6 +56,7 @@ def _signatures() -> dict:
         "psh_probe_scan": [i32, i32, vp, vp, vp, vp, vp, vp, i32, vp],
         "psh_probe_fast_div": [vp, vp, vp, vp, i64, vp],
         "psh_probe_unit_queue": [vp, i32, vp, vp, i32, vp],
+        "psh_probe_long": [i32, vp, vp, vp, vp, i32, vp],
     }
 
 
@@ -61,7 +65,7 @@ EXPORTS = tuple(SIGNATURES)
 
 
 def source_hash() -> str:
-    """SHA-256 over the probe's source, the four headers and the flags (names + contents), as _build.source_hash."""
+    """SHA-256 over the probe's source, the five headers and the flags (names + contents), as _build.source_hash."""
     h = hashlib.sha256()
     for p in DEPS:
         h.update(p.name.encode())

@@ -59,3 +59,53 @@ def rank_list(hist: np.ndarray, limit: int = 160) -> np.ndarray:
     total = int(hist.astype(np.uint64).sum())
     r = np.concatenate([[0, 1, total, total + 1, 0xffffffff], cum, cum + 1]).astype(np.uint64)
     return np.unique(r[r <= 0xffffffff]).astype(np.uint32)
+
+
+# ---------------------------------------------------------------------------------- the long-window front end (psh_long.h)
+LONG_NVALID = (1, 31, 32, 33, 512, 1023, 1024)
+LONG_OPERAND_W = (26, 126, 256)
+LONG_TABLE_CASES = tuple((nq, W) for nq in (1, 3) for W in (26, 64, 126, 256))        # the buckets 6, 6, 10, 18 ...
+LONG_TABLE_W14 = 190                                                                   # ... and 14
+LONG_EXACT_W = (26, 33, 34, 127, 256)
+LONG_BOUND_SEXP = (-60, 0, 3, 60)
+
+
+def long_stage_cases():
+    """(ensemble [R, T], T, [(row, seg_start, nfloat)]) lists: rows at odd float offsets (T odd), a row shorter than the
+    segment, a last segment of five floats with the next row behind it in memory, a first and a later row.  The ensemble is
+    followed by a margin of a whole segment, so that no load leaves the allocation whatever the range check does."""
+    g = np.random.default_rng(11)
+    out = []
+    for T, cases in ((1029, [(0, 0, 1023 + 34), (3, 0, 1023 + 256), (0, 1024, 1023 + 64), (2, 1024, 1023 + 256)]),
+                     (700, [(0, 0, 1023 + 126), (4, 0, 1023 + 33)]),
+                     (2301, [(1, 1024, 1023 + 126), (3, 2048, 1023 + 255)])):
+        ds = g.standard_normal((6, T)).astype(np.float32)
+        out.append((ds, T, cases))
+    return out
+
+
+def long_prefix_sums(seed: int) -> np.ndarray:
+    """1280 float32 prefix sums of squares at the scale the kernels see (samples of a few units), not exact in float32"""
+    g = np.random.default_rng(seed)
+    return np.concatenate([[0.0], np.cumsum(g.standard_normal(1279) ** 2 * 9.0)]).astype(np.float32)
+
+
+def long_tiles():
+    """[(tile [64, 16], nvalid)]: random tiles, a NaN in a slot that exists and in one that does not, per nvalid"""
+    g = np.random.default_rng(12)
+    out = []
+    for nv in LONG_NVALID:
+        t = (g.standard_normal((64, 16)) * 100.0).astype(np.float32)
+        t[0, 0] = np.nan                                   # window 0: exists for every nvalid
+        t[63, 15] = np.nan                                 # window 1023: exists only when nvalid = 1024
+        t[40, 9] = -1.0e6                                  # window 680, below everything: counts only when nvalid > 680
+        out.append((t, nv))
+    return out
+
+
+def long_bound_inputs():
+    """(est [64], nx [64]): est / nx around 1 / 6, a zero, an inf and a NaN estimate"""
+    nx = np.float32(37.5) * (np.float32(1.0) + np.arange(64, dtype=np.float32) / np.float32(64.0))
+    est = (nx * (np.float32(1.0 / 6.0) + (np.arange(64, dtype=np.float32) - 32) * np.float32(2.0 ** -20))).astype(np.float32)
+    est[0], est[1], est[2] = 0.0, np.inf, np.nan
+    return est, nx.astype(np.float32)

@@ -1,6 +1,7 @@
-// psh_probe.hip -- TEST INFRASTRUCTURE ONLY: one thin kernel around each primitive of psh_wave.h and psh_sort_lds.h (and
-// fast_div of psh_device.h, unit_queue of psh_segment.h), so that tests/test_gpu_wave_primitives.py and
-// tests/test_gpu_sort_primitives.py can compare each of them, bit for bit, with the numpy twins of tests/_wave_twin.py.
+// psh_probe.hip -- TEST INFRASTRUCTURE ONLY: one thin kernel around each primitive of psh_wave.h, psh_sort_lds.h and
+// psh_long.h (and fast_div of psh_device.h, unit_queue of psh_segment.h), so that tests/test_gpu_wave_primitives.py,
+// tests/test_gpu_sort_primitives.py and tests/test_gpu_long_primitives.py can compare each of them, bit for bit, with the
+// numpy twins of tests/_wave_twin.py and tests/_long_twin.py.
 // Built by tests/_probe.py with the product's flags into tests/csrc/lib/libpsh_probe.so; nothing in shadowing_amd/ links
 // or loads it and libpsh_hip.so exports none of its symbols.
 //
@@ -12,6 +13,7 @@
 #include <stdint.h>
 
 #include "psh_device.h"
+#include "psh_long.h"
 #include "psh_segment.h"
 #include "psh_sort_lds.h"
 #include "psh_wave.h"
@@ -226,6 +228,93 @@ __global__ __launch_bounds__(64) void unit_queue_kernel(const unsigned* n, int n
     }
 }
 
+// ---------------------------------------------------------------------------------- the long-window front end (psh_long.h)
+// One WAVE per case, all cases of a piece in one launch: block c reads its PSH_PROBE_LONG_PARAMS ints at par + c * that.
+#define PSH_PROBE_LONG_PARAMS 136
+enum { L_STAGE0 = 0, L_STAGE2 = 1, L_OPERAND_LO = 2, L_OPERAND_HI = 3, L_TILE_MIN = 4, L_TABLES = 5, L_EXACT_SCALAR = 6,
+       L_EXACT_VECTOR = 7, L_BOUND = 8, L_ZERO = 9 };
+
+// par: {row, T, seg_start, nfloat}; out[c][4 (lane + 64 q) + i]: the staged words, all bits set where nothing is loaded
+template <int AUX>
+__global__ __launch_bounds__(64) void long_stage_kernel(const float* ds, const int* par, unsigned* out) {
+    const int lane = (int)threadIdx.x;
+    const int* p = par + (size_t)blockIdx.x * PSH_PROBE_LONG_PARAMS;
+    Stage st;
+#pragma unroll
+    for (int q = 0; q < PSH_NSTAGE; ++q) st.v[q] = f32x4{__uint_as_float(~0u), __uint_as_float(~0u), __uint_as_float(~0u), __uint_as_float(~0u)};
+    long_stage_row<AUX>(st, ds, (int64_t)p[1], (int64_t)p[0], p[2], p[3], lane);
+    unsigned* o = out + (size_t)blockIdx.x * (256 * PSH_NSTAGE);
+#pragma unroll
+    for (int q = 0; q < PSH_NSTAGE; ++q)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[4 * (lane + 64 * q) + i] = __float_as_uint(st.v[q][i]);
+}
+// in[c][PSH_LONG_SFLOATS]: prefix sums; par: {W}; out[c][16 lane + r]
+template <bool UPPER>
+__global__ __launch_bounds__(64) void long_operand_kernel(const float* in, const int* par, float* out) {
+    const int lane = (int)threadIdx.x, m = lane & 31, hk = lane >> 5;
+    const float* ps_lo = in + (size_t)blockIdx.x * PSH_LONG_SFLOATS + m + 128 * hk;
+    const f32x16 ce = long_energy_operand<UPPER>(ps_lo, ps_lo + par[(size_t)blockIdx.x * PSH_PROBE_LONG_PARAMS]);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) out[((size_t)blockIdx.x * 64 + lane) * 16 + r] = ce[r];
+}
+// in[c][16 lane + r]: a tile; par: {nvalid}; out[c][lane]
+__global__ __launch_bounds__(64) void long_tile_min_kernel(const float* in, const int* par, float* out) {
+    const int lane = (int)threadIdx.x;
+    f32x16 c;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) c[r] = in[((size_t)blockIdx.x * 64 + lane) * 16 + r];
+    out[(size_t)blockIdx.x * 64 + lane] = long_tile_min(c, par[(size_t)blockIdx.x * PSH_PROBE_LONG_PARAMS], lane);
+}
+// in[c][3][256]: queries; par: {nks bucket, nq, W, scale bits}; out[c][3 * 3328] halves: the tables as the kernels hold them
+#define PSH_PROBE_TAB_HALVES (3 * (lq_query_bytes(18) / 2))
+__global__ __launch_bounds__(64) void long_tables_kernel(const float* in, const int* par, unsigned short* out) {
+    __shared__ __attribute__((aligned(16))) float xs[3 * 256];
+    __shared__ __attribute__((aligned(16))) _Float16 tab[PSH_PROBE_TAB_HALVES];
+    const int lane = (int)threadIdx.x;
+    const int* p = par + (size_t)blockIdx.x * PSH_PROBE_LONG_PARAMS;
+    const int nks = p[0], nq = p[1], W = p[2];
+    const float scale = __uint_as_float((unsigned)p[3]);
+    for (int e = lane; e < nq * W; e += 64) xs[e] = in[(size_t)blockIdx.x * 768 + e];
+    for (int e = lane; e < PSH_PROBE_TAB_HALVES; e += 64) tab[e] = (_Float16)1.0f;          // what the call must overwrite
+    wave_lds_fence();
+    if (nks == 6) long_query_tables<6>(tab, xs, nq, W, scale, lane, 64);
+    else if (nks == 10) long_query_tables<10>(tab, xs, nq, W, scale, lane, 64);
+    else if (nks == 14) long_query_tables<14>(tab, xs, nq, W, scale, lane, 64);
+    else long_query_tables<18>(tab, xs, nq, W, scale, lane, 64);
+    wave_lds_fence();
+    for (int e = lane; e < PSH_PROBE_TAB_HALVES; e += 64) out[(size_t)blockIdx.x * PSH_PROBE_TAB_HALVES + e] = reinterpret_cast<const unsigned short*>(tab)[e];
+}
+// y, x: float arrays; par: {W, qn, x offset (scalar kind), -, t[64] at 8, x offsets[64] at 72}; out[c][lane]: the chain, 0 past qn
+template <bool VECTOR>
+__global__ __launch_bounds__(64) void long_exact_kernel(const float* y, const float* x, const int* par, float* out) {
+    const int lane = (int)threadIdx.x;
+    const int* p = par + (size_t)blockIdx.x * PSH_PROBE_LONG_PARAMS;
+    const int W = p[0];
+    float v = 0.0f;
+    if (lane < p[1]) {
+        if constexpr (VECTOR) v = long_exact_window(y + p[8 + lane], x + p[72 + lane], W);
+        else v = long_exact_window(y + p[8 + lane], (const_f32p)x + p[2], W);
+    }
+    out[(size_t)blockIdx.x * 64 + lane] = v;
+}
+// est[c][lane], nx[c][lane]; par: {W, sexp}
+__global__ __launch_bounds__(64) void long_bound_kernel(const float* est, const float* nx, const int* par, float* out) {
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    const int* p = par + (size_t)blockIdx.x * PSH_PROBE_LONG_PARAMS;
+    out[i] = long_upper_bound(est[i], nx[i], p[0], p[1]);
+}
+// par: {words}; out[c][1024]: a buffer of 1024 words, all bits set, after long_zero_rows(buffer, words, lane)
+__global__ __launch_bounds__(64) void long_zero_kernel(const int* par, unsigned* out) {
+    __shared__ __attribute__((aligned(16))) unsigned buf[1024];
+    const int lane = (int)threadIdx.x;
+    for (int e = lane; e < 1024; e += 64) buf[e] = ~0u;
+    wave_lds_fence();
+    long_zero_rows(reinterpret_cast<_Float16*>(buf), par[(size_t)blockIdx.x * PSH_PROBE_LONG_PARAMS], lane);
+    wave_lds_fence();
+    for (int e = lane; e < 1024; e += 64) out[(size_t)blockIdx.x * 1024 + e] = buf[e];
+}
+
 }  // namespace
 
 }  // namespace psh
@@ -234,7 +323,7 @@ using namespace psh;
 
 extern "C" {
 
-int psh_probe_version(void) { return 1; }
+int psh_probe_version(void) { return 2; }
 
 // type: 0 float32, 1 float64, 2 int32, 3 uint32; op: 0 sum, 1 min, 2 max, 3 or (integers), 4 minmax (lo from a, hi from b,
 // the maxima to out2), 5 wave_scan_inclusive; n lanes, whole blocks of 256
@@ -345,6 +434,32 @@ int psh_probe_unit_queue(const void* n, int nn, void* lo, void* hi, int grid, vo
     if (nn <= 0 || grid <= 0) return -1;
     hipLaunchKernelGGL(unit_queue_kernel, dim3((unsigned)grid), dim3(64), 0, (hipStream_t)stream, (const unsigned*)n, nn,
                        (unsigned*)lo, (unsigned*)hi);
+    return (int)hipGetLastError();
+}
+
+// the pieces of psh_long.h, one wave per case: what = 0 / 1 long_stage_row<0> / <2> (a = the ensemble), 2 / 3
+// long_energy_operand<false> / <true> (a = prefix sums), 4 long_tile_min (a = tiles), 5 long_query_tables (a = queries),
+// 6 / 7 long_exact_window with a scalar / a per-lane query pointer (a = y, b = x), 8 long_upper_bound (a = est, b = nx),
+// 9 long_zero_rows; par: ncases x 136 ints, laid out as the kernels above say
+int psh_probe_long(int what, const void* a, const void* b, const void* par, void* out, int ncases, void* stream) {
+    if (ncases <= 0) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)ncases), block(64);
+    const float *fa = (const float*)a, *fb = (const float*)b;
+    const int* p = (const int*)par;
+    switch (what) {
+    case L_STAGE0: hipLaunchKernelGGL((long_stage_kernel<0>), grid, block, 0, s, fa, p, (unsigned*)out); break;
+    case L_STAGE2: hipLaunchKernelGGL((long_stage_kernel<2>), grid, block, 0, s, fa, p, (unsigned*)out); break;
+    case L_OPERAND_LO: hipLaunchKernelGGL((long_operand_kernel<false>), grid, block, 0, s, fa, p, (float*)out); break;
+    case L_OPERAND_HI: hipLaunchKernelGGL((long_operand_kernel<true>), grid, block, 0, s, fa, p, (float*)out); break;
+    case L_TILE_MIN: hipLaunchKernelGGL(long_tile_min_kernel, grid, block, 0, s, fa, p, (float*)out); break;
+    case L_TABLES: hipLaunchKernelGGL(long_tables_kernel, grid, block, 0, s, fa, p, (unsigned short*)out); break;
+    case L_EXACT_SCALAR: hipLaunchKernelGGL((long_exact_kernel<false>), grid, block, 0, s, fa, fb, p, (float*)out); break;
+    case L_EXACT_VECTOR: hipLaunchKernelGGL((long_exact_kernel<true>), grid, block, 0, s, fa, fb, p, (float*)out); break;
+    case L_BOUND: hipLaunchKernelGGL(long_bound_kernel, grid, block, 0, s, fa, fb, p, (float*)out); break;
+    case L_ZERO: hipLaunchKernelGGL(long_zero_kernel, grid, block, 0, s, p, (unsigned*)out); break;
+    default: return -1;
+    }
     return (int)hipGetLastError();
 }
 

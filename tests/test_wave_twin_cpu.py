@@ -216,3 +216,87 @@ def test_product_never_mentions_the_probe():
         if p.is_file() and p.suffix in (".py", ".hip", ".h", ".cpp", ".c"):
             assert not re.search(r"\b_probe\b|psh_probe", p.read_text()), p      # (the module tests/_probe.py, the library)
     assert not any("probe" in p.name for p in _build.SOURCES + _build.DEPS)
+
+
+# ------------------------------------------------------------------------------------------ the long-window twins
+import _long_twin as lt  # noqa: E402
+from fractions import Fraction  # noqa: E402
+
+
+def test_round_f32_is_round_to_nearest_even():
+    one, ulp = Fraction(1), Fraction(2) ** -23
+    assert lt.round_f32(one + ulp / 2) == np.float32(1.0)                           # a tie: to the even neighbour
+    assert lt.round_f32(one + ulp * 3 / 2) == np.float32(1.0) + np.float32(2.0 ** -22)
+    assert lt.round_f32(one + ulp / 2 + Fraction(2) ** -80) == np.float32(1.0) + np.float32(2.0 ** -23)
+    assert lt.round_f32(Fraction(2) ** -150) == 0 and lt.round_f32(Fraction(2) ** -150 * 3) == np.float32(2.0 ** -148)
+    assert lt.round_f32(Fraction(2) ** 128 - Fraction(2) ** 103) == np.inf and lt.round_f32(-(Fraction(2) ** 128)) == -np.inf
+    g = np.random.default_rng(5)
+    for x in g.standard_normal(200) * 10.0 ** g.integers(-30, 30, 200):
+        assert lt.round_f32(Fraction(float(x))) == np.float32(x)                    # float64 -> float32 is one rounding too
+    # an fma a float64 product-and-add gets wrong: the product's low bits decide a tie
+    a, b, c = np.float32(1 + 2.0 ** -12), np.float32(1 + 2.0 ** -12), np.float32(2.0 ** 30)
+    assert lt.fma32(a, b, c) == lt.round_f32(Fraction(float(a)) ** 2 + Fraction(float(c)))
+
+
+def test_energy_operand_twin_against_the_formula():
+    sp = cases.long_prefix_sums(3)
+    for W in cases.LONG_OPERAND_W:
+        for upper in (False, True):
+            ce = lt.energy_operand(sp, W, upper)
+            lane, r = np.meshgrid(np.arange(64), np.arange(16), indexing="ij")
+            p = lt.mx_window(r, lane)
+            assert sorted(p.ravel()) == list(range(1024))                             # the map covers the segment once
+            S = sp.astype(np.float64)
+            want = S[p + W] * (1.0 + (2.0 ** -17 if upper else -(2.0 ** -17))) - S[p]
+            assert np.all(np.abs(ce - want) <= 2.0 ** -24 * np.abs(want) * 1.0000001 + 1e-30)       # half an ulp of the result
+            E = S[p + W] - S[p]
+            assert np.all(ce >= E) if upper else np.all(ce <= E)
+
+
+def test_tile_min_twin_against_a_plain_minimum():
+    for tile, nv in cases.long_tiles():
+        lane, r = np.meshgrid(np.arange(64), np.arange(16), indexing="ij")
+        valid = lt.mx_window(r, lane) < nv
+        want = np.nanmin(np.where(valid, tile, np.inf))
+        got = lt.tile_min(tile, nv)
+        assert np.all(got == np.float32(want)), nv
+
+
+def test_query_tables_twin_against_the_formula():
+    g = np.random.default_rng(6)
+    for nq, W in cases.LONG_TABLE_CASES + ((3, cases.LONG_TABLE_W14),):
+        nks = lt.bucket(W)
+        xs = g.standard_normal((nq, W)).astype(np.float32)
+        tab = lt.query_tables(xs, W, 0.5, nks)
+        assert tab.shape == (nq, 8, lt.copy_chunks(nks), 8) and tab.size == nq * lt.query_halves(nks)
+        # the fragment of lane (n, hk), K-step s is chunk 2 s + hk - (n >> 3) + 3 of copy n & 7: -2 x~[16 s + 8 hk + i - n]
+        for n in (0, 7, 8, 31):
+            for hk in (0, 1):
+                for s in range(lt.ksteps(W)):
+                    frag = tab[:, n & 7, 2 * s + hk - (n >> 3) + 3, :]
+                    j = 16 * s + 8 * hk + np.arange(8) - n
+                    want = np.where((j >= 0) & (j < W), -2.0 * (xs[:, np.clip(j, 0, W - 1)] * np.float32(0.5)), 0.0)
+                    assert np.array_equal(frag, want.astype(np.float16))
+    assert sorted({lt.bucket(W) for _, W in cases.LONG_TABLE_CASES} | {lt.bucket(cases.LONG_TABLE_W14)}) == [6, 10, 14, 18]
+
+
+def test_exact_window_and_upper_bound_twins():
+    g = np.random.default_rng(7)
+    x, y = g.standard_normal(40).astype(np.float32), g.standard_normal(40).astype(np.float32)
+    v = lt.exact_window(y, x, 40)
+    want = ((x.astype(np.float64) - y.astype(np.float64)) ** 2).sum()
+    assert abs(float(v) - want) <= 41 * 2.0 ** -24 * want
+    est, nx = cases.long_bound_inputs()
+    for sexp in cases.LONG_BOUND_SEXP:
+        ub = lt.upper_bound(est, nx, 126, sexp)
+        assert ub.dtype == np.float32 and np.isposinf(ub[1]) and np.isposinf(ub[2])
+        fin = np.isfinite(ub)
+        plain = (est.astype(np.float64) + nx * (3.0 / 900.0) + 254.0 / 64.0 / 262144.0) * (1.0 + 2.0 / 900.0 + 1e-5 + 6.0 * 2.0 ** -17) * (1.0 + 1e-6) * 4.0 ** -sexp
+        assert np.allclose(ub[fin], plain[fin], rtol=1e-6)
+
+
+def test_stage_row_twin_reads_zero_past_the_row():
+    ds, T, cs = cases.long_stage_cases()[0]
+    w = lt.stage_row(ds, T, 0, 1024, 1023 + 64)
+    assert np.array_equal(w[:5].view(np.float32), ds[0, 1024:]) and not w[5:4 * 272].any()       # ... although row 1 follows
+    assert np.all(w[4 * 272:] == 0xffffffff)                                                       # ceil(1087 / 4) = 272 pieces
