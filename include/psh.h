@@ -641,6 +641,40 @@ int psh_softmax_weights(int device, void* stream, const float* distances, int B,
                         const double* etas, int n_etas, const int* ks, int n_ks, double* out_weights);
 
 /*
+ * Time-separated nearest windows: the exclusion zone of subsequence search on the list a scan returns.  The K nearest
+ * SLIDING windows of a query may hold windows t and t + 1 of one trajectory, which share all but one of their future
+ * samples; this entry keeps, of every group of such near-copies, the nearest.  d: device B x K float32; idx: device
+ * B x K x 2 int32 = [r, t], as psh_scan_topk leaves them.  For one query, with its K entries (d_i, r_i, t_i) in the order
+ * given (the scans hand them over ascending in (d, r, t)) and delta >= 0 an integer number of samples:
+ *     keep_i  =  r_i >= 0  and  there is no j < i with keep_j, r_j == r_i and |t_j - t_i| <= delta
+ * The rule reads positions and indices only, never d.  Row b of the outputs holds the first k kept entries in list order:
+ *   out_d     device B x k float32: the input's bits, NaN included;
+ *   out_idx   device B x k x 2 int32: [r, t];
+ *   out_pos   device B x k int32: the position i in the input list (a caller who has gathered the K paths picks rows by it);
+ *   out_count device B int32: the number kept among all K; it may exceed k;
+ *   out_status device B int32: PSH_SEPARATE_STATUS_SHORT when out_count[b] < k; the slots past the count then hold +inf,
+ *             (-1, -1) and -1.
+ * What follows from the rule:
+ *   - Prefix exactness: whether entry i is kept depends on the entries before i only.  So the kept entries of an exact
+ *     top-K list are exactly the first kept entries of the greedy walk over ALL windows, and if out_count >= k the answer
+ *     is exact whatever K was: over-asking the scan and separating is rigorous.
+ *   - delta = 0 returns the first k entries with r >= 0 (two entries never share (r, t)).
+ *   - An entry with r < 0 is padding: never kept, and it suppresses nothing.  t >= 0 wherever r >= 0.
+ *   - Kept entries of one row are more than delta apart pairwise; every dropped entry has a kept entry of its row within
+ *     delta at a smaller position.
+ *   - delta goes up to 2^31 - 1 with r, t < 2^31: |t_j - t_i| is formed as a difference, nothing is added to delta.
+ *   - The result of a query does not depend on the other queries of the call.
+ *   - No atomics and no floating-point arithmetic at all: two calls give identical bits.
+ * Stream-ordered: no workspace, no allocation, no synchronisation; capturable into a graph.
+ * A NULL pointer, B, K or k < 1, k > K, or delta < 0: PSH_ERR_ARG before anything touches the device; K > PSH_MAX_K:
+ * PSH_ERR_UNSUPPORTED.  The method heads shadowing_amd/csrc/psh_separate.hip; shadowing_amd/separation.py is its numpy twin.
+ */
+#define PSH_SEPARATE_STATUS_OK     0
+#define PSH_SEPARATE_STATUS_SHORT  1   /* fewer than k of the K entries are kept */
+int psh_separate_topk(int device, void* stream, const float* d, const int32_t* idx, int B, int K, int k, int delta,
+                      float* out_d, int32_t* out_idx, int32_t* out_pos, int32_t* out_count, int32_t* out_status);
+
+/*
  * Hedged Monte Carlo (Potters, Bouchaud, Sestovic 2001) on the k shadowing paths of each of B dates: the option prices,
  * Black-Scholes implied vols and strikes of a smile.  The method, in full, heads shadowing_amd/csrc/psh_hmc.hip (and
  * README "Option pricing"); shadowing_amd/pricing.py is its numpy twin.

@@ -19,6 +19,7 @@ from .quantiles import PredictiveQuantiles, weighted_quantiles
 from .scoring import EnsembleScore, score_ensemble
 from .statistics import realized_variance
 from .weights import softmax_weights
+from .separation import Separated, separate_topk
 from .calibration import Calibration, MarketQuotes, calibrate_host, calibrate_weights
 from .stylized import LaggedMoments, fit_smrw, lagged_moments
 from .scattering import (ScatteringSpectra, scattering_bank, scattering_generate, scattering_loss, scattering_spectra,
@@ -34,6 +35,6 @@ __all__ = [
     "smrw_sq_moment", "LaggedMoments", "lagged_moments", "fit_smrw",
     "ScatteringSpectra", "scattering_spectra", "scattering_bank", "scattering_sums", "scattering_loss",
     "scattering_generate", "PredictiveQuantiles", "weighted_quantiles", "EnsembleScore", "score_ensemble",
-    "softmax_weights", "Calibration", "MarketQuotes", "calibrate_weights", "calibrate_host",
+    "softmax_weights", "Separated", "separate_topk", "Calibration", "MarketQuotes", "calibrate_weights", "calibrate_host",
 ]
 __version__ = "0.1.0"

@@ -12,7 +12,7 @@ LIBDIR = PKG / "lib"
 LIB = LIBDIR / "libpsh_hip.so"
 INCLUDE = PKG.parent / "include"
 SOURCES = [CSRC / "psh_scan.hip", CSRC / "psh_fused.hip", CSRC / "psh_stream.hip", CSRC / "psh_stream_copy.hip", CSRC / "psh_lq.hip", CSRC / "psh_embed.hip", CSRC / "psh_embed_px.hip", CSRC / "psh_embed_mx.hip", CSRC / "psh_select.hip",
-           CSRC / "psh_capi.hip", CSRC / "psh_comm.hip", CSRC / "psh_predict.hip", CSRC / "psh_prep.hip", CSRC / "psh_hmc.hip", CSRC / "psh_hmc_report.hip", CSRC / "psh_pdv.hip", CSRC / "psh_mrw.hip", CSRC / "psh_smrw.hip", CSRC / "psh_moments.hip", CSRC / "psh_scattering.hip", CSRC / "psh_scattering_grad.hip", CSRC / "psh_quantiles.hip", CSRC / "psh_scoring.hip", CSRC / "psh_weights.hip", CSRC / "psh_calibrate.hip"]
+           CSRC / "psh_capi.hip", CSRC / "psh_comm.hip", CSRC / "psh_predict.hip", CSRC / "psh_prep.hip", CSRC / "psh_hmc.hip", CSRC / "psh_hmc_report.hip", CSRC / "psh_pdv.hip", CSRC / "psh_mrw.hip", CSRC / "psh_smrw.hip", CSRC / "psh_moments.hip", CSRC / "psh_scattering.hip", CSRC / "psh_scattering_grad.hip", CSRC / "psh_quantiles.hip", CSRC / "psh_scoring.hip", CSRC / "psh_weights.hip", CSRC / "psh_calibrate.hip", CSRC / "psh_separate.hip"]
 DEPS = SOURCES + [CSRC / "psh_kernels.h", CSRC / "psh_device.h", CSRC / "psh_wave.h", CSRC / "psh_segment.h", CSRC / "psh_long.h", CSRC / "psh_philox.h", CSRC / "psh_mrw_lds.h", CSRC / "psh_scat_lds.h", CSRC / "psh_hmc_body.h", CSRC / "psh_sort_lds.h", CSRC / "psh_launch.h", INCLUDE / "psh.h"]
 
 # -ffp-contract=off: nothing may be fused or re-associated that the source does not

@@ -100,6 +100,7 @@ def _signatures() -> dict:
         "psh_weighted_quantiles": [i32, vp, vp, vp, i32, i32, i32, P(f64), i32, vp, vp, vp, vp],
         "psh_score_ensemble": [i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
         "psh_softmax_weights": [i32, vp, vp, i32, i32, P(f64), i32, P(i32), i32, vp],
+        "psh_separate_topk": [i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
         "psh_realized_variance": [i32, vp, vp, i64, i64, i32, P(i32), i32, i32, vp],
         "psh_calibrate_workspace_bytes": [i32, i32, i32, P(sz)],
         "psh_calibrate_weights": [i32, vp, vp, i64, i32, i32, i32, vp, f64, f64, P(i32), i32, vp, vp, i32, i32, i32, f64, f64, i32,
@@ -1166,6 +1167,34 @@ def softmax_weights(distances: torch.Tensor, etas, ks=None) -> torch.Tensor:
                                       len(es), None if kk is None else (C.c_int * n_ks)(*kk), n_ks, out.data_ptr()),
            "psh_softmax_weights")
     return out
+
+
+PSH_SEPARATE_STATUS_OK, PSH_SEPARATE_STATUS_SHORT = 0, 1
+
+
+def separate_topk(distances: torch.Tensor, indices: torch.Tensor, k: int, delta: int):
+    """psh_separate_topk on the (B, K) float32 distances and (B, K, 2) int32 indices of a scan, where they lie: the first k
+    entries an exclusion zone of `delta` samples keeps, as device tensors (distances (B, k), indices (B, k, 2), positions
+    (B, k) int32, count (B,) int32, status (B,) int32); nothing is synchronised here."""
+    d = _dev_tensor(distances, torch.float32, "distances")
+    idx = _dev_tensor(indices, torch.int32, "indices")
+    if d.dim() != 2 or d.numel() == 0 or tuple(idx.shape) != tuple(d.shape) + (2,):
+        raise ValueError(f"distances must be (B, K), not empty, and indices (B, K, 2); got {tuple(d.shape)} and {tuple(idx.shape)}")
+    B, K = d.shape
+    k, delta = int(k), int(delta)
+    if not (1 <= k <= K) or not (0 <= delta < 2 ** 31):
+        raise ValueError(f"separate_topk: 1 <= k <= K = {K} and 0 <= delta < 2^31, got k = {k}, delta = {delta}")
+    if K > PSH_MAX_K:
+        raise NativeLibraryError(f"psh_separate_topk takes lists of K <= {PSH_MAX_K} entries, got {K}")
+    od = torch.empty((B, k), dtype=torch.float32, device=d.device)
+    oi = torch.empty((B, k, 2), dtype=torch.int32, device=d.device)
+    op = torch.empty((B, k), dtype=torch.int32, device=d.device)
+    oc = torch.empty(B, dtype=torch.int32, device=d.device)
+    os_ = torch.empty(B, dtype=torch.int32, device=d.device)
+    _check(load().psh_separate_topk(d.device.index, _stream_ptr(d.device), d.data_ptr(), idx.data_ptr(), B, K, k, delta,
+                                    od.data_ptr(), oi.data_ptr(), op.data_ptr(), oc.data_ptr(), os_.data_ptr()),
+           "psh_separate_topk")
+    return od, oi, op, oc, os_
 
 
 def _uniform_rows(x: torch.Tensor):

@@ -1549,6 +1549,20 @@ int psh_softmax_weights(int device, void* stream, const float* distances, int B,
     return PSH_OK;
 }
 
+int psh_separate_topk(int device, void* stream, const float* d, const int32_t* idx, int B, int K, int k, int delta,
+                      float* out_d, int32_t* out_idx, int32_t* out_pos, int32_t* out_count, int32_t* out_status) {
+    if (!d || !idx || !out_d || !out_idx || !out_pos || !out_count || !out_status || B <= 0 || K <= 0 || k <= 0 || k > K ||
+        delta < 0)
+        return PSH_ERR_ARG;
+    if (K > PSH_MAX_K) return PSH_ERR_UNSUPPORTED;                          // (one workgroup per query, the list in LDS)
+    SeparateArgs a{};
+    a.d = d; a.idx = idx; a.B = B; a.K = K; a.k = k; a.delta = delta;
+    a.out_d = out_d; a.out_idx = out_idx; a.out_pos = out_pos; a.out_count = out_count; a.out_status = out_status;
+    GUARD_DEVICE(device);
+    HIP_TRY(launch_separate(a, (hipStream_t)stream));
+    return PSH_OK;
+}
+
 int psh_calibrate_workspace_bytes(int B, int k, int nT, size_t* out) {
     if (!out || B <= 0 || k <= 0 || nT <= 0) return PSH_ERR_ARG;
     if (k > PSH_MAX_K || nT > PSH_CAL_MAX_INSTRUMENTS) return PSH_ERR_UNSUPPORTED;

@@ -443,6 +443,19 @@ struct WeightsArgs {
 };
 hipError_t launch_softmax_weights(const WeightsArgs& a, hipStream_t s);
 
+// psh_separate.hip: the first k entries of a (B, K) list that an exclusion zone of delta samples keeps (psh_separate_topk)
+struct SeparateArgs {
+    const float* d;           // (B, K)
+    const int32_t* idx;       // (B, K, 2) = [r, t]; r < 0: padding
+    int B, K, k, delta;
+    float* out_d;             // (B, k)
+    int32_t* out_idx;         // (B, k, 2)
+    int32_t* out_pos;         // (B, k)
+    int32_t* out_count;       // (B)
+    int32_t* out_status;      // (B)
+};
+hipError_t launch_separate(const SeparateArgs& a, hipStream_t s);
+
 // psh_calibrate.hip: the paths' weights calibrated to quoted vanillas (psh_calibrate_weights)
 struct CalArgs {
     const float* x;           // log-returns, row (b * k + i) at x + (b * k + i) * row_stride

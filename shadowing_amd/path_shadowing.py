@@ -99,7 +99,8 @@ class PathShadowing:
     """
 
     def __init__(self, embedding: PathEmbedding, distance: PathDistance,
-                 dataset, context: ContextManagerBase | None = None, cache: bool | str = "auto", hint: str | None = None):
+                 dataset, context: ContextManagerBase | None = None, cache: bool | str = "auto", hint: str | None = None,
+                 separation: int | None = None):
         """`cache` governs the copy of the ensemble kept in HBM for cuda=True (the reference re-reads and
         re-uploads `dataset` on every call, ref :205, :154-155):
           "auto" (default)  kept only when staleness is detectable or impossible: a torch tensor (CUDA: used in
@@ -116,13 +117,23 @@ class PathShadowing:
                             grid barrier.  A hint that falls short (fewer than k windows below it, or more than the candidate
                             lists hold) costs one more launch without it and switches the hints off for a few calls
                             (`last_hint` says what happened) -- results are the exact top-k either way.  Pays for rolling query
-                            dates whose k-th distance moves by a few per cent from date to date; not for unrelated queries."""
+                            dates whose k-th distance moves by a few per cent from date to date; not for unrelated queries.
+        `separation` (README "Separated neighbours"): None (default) returns the k nearest sliding windows, as the reference
+        does; a non-negative int Delta returns the k nearest windows that an exclusion zone of Delta samples keeps -- a window
+        is dropped when a nearer kept window of its row starts within Delta samples of it (separation.py) -- on every route
+        and in every flow; `last_separation` says what it took."""
         if isinstance(dataset, Path) or hasattr(dataset, "load"):
             dataset = self._load_with_scatspectra(dataset)
         if cache not in (True, False, "auto"):
             raise ValueError('cache must be True, False or "auto"')
         if hint not in (None, "auto"):
             raise ValueError('hint must be None or "auto"')
+        if separation is not None and (isinstance(separation, bool) or not isinstance(separation, (int, np.integer))
+                                       or not 0 <= separation < 2 ** 31):
+            raise ValueError("separation must be None or an int in 0 .. 2^31 - 1 (the exclusion zone, in samples)")
+        self.separation = None if separation is None else int(separation)
+        self.last_separation = None  # {"delta", "K": the list length that served, "scans", "count": kept per query at that K}
+        self._sep_pending = None     # last_separation of a deferred scan, its counts still on the device (_scan_then)
         self.hint = hint
         self._hint_state = None     # {"dk": relative k-th distance of the last call, "k", "W", "skip": calls left without a hint, "fails"}
         self.last_hint = None       # None: the last call gave no hint; "ok" / "short": what became of the one it gave
@@ -345,10 +356,56 @@ class PathShadowing:
             self._scan_rows = (key, rows, ds)
         return self._scan_rows[1]
 
-    def _native_scan(self, x: torch.Tensor, y: torch.Tensor, k: int, defer_status: bool = False):
+    def _native_scan(self, x: torch.Tensor, y: torch.Tensor, k: int, defer_status: bool = False, resume=None):
         """(d, idx, resident dataset) on the device.  `defer_status` (Identity scans only): ONE raw call, its status
         tensor returned as a fourth item instead of being waited for -- the caller reads it together with the results
-        (one synchronisation per call instead of two) and comes back without the flag when it is not zero."""
+        (one synchronisation per call instead of two) and comes back without the flag when it is not zero.
+        With a `separation` the scan asks for K1 = min(cap, k + max(64, k // 4)) windows, cap = min(PSH_MAX_K, windows),
+        psh_separate_topk is enqueued behind it and its (B, k) results are handed on; under `defer_status` its SHORT word
+        rides the status (x 4) and the kept counts wait in `_sep_pending`.  The checked route rescans the queries that came
+        back short with K doubled up to cap (`resume`: (scans so far, K to go on with)) -- any K with count >= k gives the
+        same answer -- and a query still short at cap sends the call to the generic formulation (`_served_by` "torch")."""
+        if self.separation is None:
+            return self._native_scan_raw(x, y, k, defer_status)
+        delta, h = self.separation, self.context.get_out_times()
+        n_windows = y.shape[0] * (y.shape[-1] - x.shape[-1] - h + 1)
+        if k > n_windows:
+            raise RuntimeError("selected index k out of range")
+        cap = min(_native.PSH_MAX_K, n_windows)
+        scans, K = resume or (0, k + max(64, k // 4))
+        K = min(cap, K)
+        if defer_status and self._native_kind(x, y, k) == "identity":
+            d, idx, ds, st = self._native_scan_raw(x, y, K, True)
+            sd, si, _, sc, ss = _native.separate_topk(d.contiguous(), idx.contiguous(), k, delta)
+            self._sep_pending = {"delta": delta, "K": K, "scans": 1, "count": sc}
+            return sd, si, ds, st + 4 * ss
+        B = x.shape[0]
+        todo, counts, od, oi = torch.arange(B), np.zeros(B, dtype=np.int32), None, None
+        while True:
+            d, idx, ds = self._native_scan_raw(x if todo.numel() == B else x[todo], y, K)[:3]
+            scans += 1
+            sd, si, _, sc, _ = _native.separate_topk(d.contiguous(), idx.contiguous(), k, delta)
+            cnt = sc.cpu().numpy()
+            if od is None:
+                od, oi = sd, si
+            else:
+                sel = todo.to(od.device)
+                od[sel], oi[sel] = sd, si
+            counts[todo.numpy()] = cnt
+            short = torch.from_numpy(cnt < k)
+            if not bool(short.any()):
+                self.last_separation = {"delta": delta, "K": K, "scans": scans, "count": counts}
+                return od, oi, ds
+            if K >= cap:
+                break
+            todo, K = todo[short], min(cap, 2 * K)
+        dev = self._hip_device()
+        d, idx = self._generic_scan(x, y, k, 1, True)
+        self._served_by = "torch"
+        return d.to(dev), idx.to(dev), self._resident_dataset(y, dev)
+
+    def _native_scan_raw(self, x: torch.Tensor, y: torch.Tensor, k: int, defer_status: bool = False):
+        """_native_scan's (d, idx, resident dataset[, status]) for the k nearest sliding windows."""
         dev = self._hip_device()
         _native.load()
         self._served_by = "hip"
@@ -440,6 +497,30 @@ class PathShadowing:
 
     # ------------------------------------------------------------------ generic path
     def _generic_scan(self, x: torch.Tensor, y: torch.Tensor, k: int, n_splits: int, cuda: bool):
+        """(d, idx) of the generic formulation as CPU tensors.  With a `separation`: the scan at K = k + max(64, k // 4),
+        doubled up to the number of windows while a query keeps fewer than k, then the numpy twin of psh_separate_topk."""
+        if self.separation is None:
+            return self._generic_scan_raw(x, y, k, n_splits, cuda)
+        from .separation import separate_topk
+        with torch.no_grad():                                     # (one row through the scanning embedding: the windows a row has)
+            scanner = self.embedding.adjust_to_context(self.context)
+            n_windows = y.shape[0] * math.prod(scanner(y[:1].to(self.embedding.kernel.device)).shape[1:-1])
+        if k > n_windows:
+            raise RuntimeError("selected index k out of range")
+        K, scans = min(n_windows, k + max(64, k // 4)), 0
+        while True:
+            d, idx = self._generic_scan_raw(x, y, K, n_splits, cuda)
+            scans += 1
+            sep = separate_topk(d.numpy(), idx.numpy(), k, self.separation, cuda=False)
+            if not (sep.count < k).any():
+                self.last_separation = {"delta": self.separation, "K": K, "scans": scans, "count": sep.count}
+                return torch.from_numpy(sep.distances), torch.from_numpy(sep.indices)
+            if K >= n_windows:
+                raise RuntimeError(f"fewer than k windows more than separation = {self.separation} samples apart in the "
+                                   f"dataset: a query keeps {int(sep.count.min())} of its {n_windows} windows, k = {k}")
+            K = min(n_windows, 2 * K)
+
+    def _generic_scan_raw(self, x: torch.Tensor, y: torch.Tensor, k: int, n_splits: int, cuda: bool):
         """The reference's formulation with stock torch ops (ref :129-177): embed the
         query, pad the kernel by the context, then per dataset split: embed, broadcast
         distance, top-k, decode, merge with the running best."""
@@ -495,7 +576,7 @@ class PathShadowing:
         ksize = self.embedding.kernel.shape[-1]
         if ksize != 0 and ksize != x_context.shape[-1]:
             raise Exception("The embedding kernel should be of the same size as the context.")
-        if cuda and self._fast is not None:
+        if cuda and self._fast is not None and self.separation is None:
             got = self._shadow_fast(self._fast, x_context, k)
             if got is not None:
                 return got
@@ -503,7 +584,7 @@ class PathShadowing:
         y = self._dataset_tensor()
         length = x.shape[-1] + self.context.get_out_times()
 
-        if cuda and x.shape[0] == 1 and self._native_kind(x, y, k) == "identity":
+        if cuda and x.shape[0] == 1 and self.separation is None and self._native_kind(x, y, k) == "identity":
             # one Identity query: a prepared slot (argument lists, pinned staging, result buffers built once) on the caller's
             # stream, the fused single launch -- 214 -> 162 us per call at the benchmark size, the kernels' 100 included
             got = self._shadow_prepared(x, y, k)
@@ -532,12 +613,19 @@ class PathShadowing:
         self.last_path = self._served_by
         if len(out) == 4:
             kept, down = consume(*out[:3])
-            *host, hs = self._to_host(*down, out[3])
+            pend = self._sep_pending if self.separation is not None else None
+            *host, hs = self._to_host(*down, *((pend["count"],) if pend else ()), out[3])
+            if pend:
+                pend["count"] = host.pop()
             if not hs.any():
+                self.last_separation = pend
                 return kept, tuple(host)
-            if bool((hs == _native.PSH_STATUS_RETRY).any()):
+            if bool(((hs & 3) == _native.PSH_STATUS_RETRY).any()):
                 self._workspace.arm()
-            out = self._native_scan(x, y, k)
+            # (only the separation came back short: the checked route goes on from the list length after this one)
+            resume = (1, min(2 * pend["K"], _native.PSH_MAX_K)) if pend and not (hs & 3).any() else None
+            out = self._native_scan(x, y, k, resume=resume)
+            self.last_path = self._served_by
         kept, down = consume(*out)
         return kept, (self._to_host(*down) if down else ())
 
@@ -659,6 +747,9 @@ class PathShadowing:
         a stream of calls costs ~85 us each at the benchmark size where blocking calls cost ~160 (launch + results).  The
         reference has no counterpart (its shadow() is blocking, ref :181-218); any configuration this path does not cover is
         served by shadow() itself at call time and handed back through the same handle."""
+        if self.separation is not None:
+            raise ValueError("shadow_async serves the k nearest sliding windows from prepared one-query slots; with a "
+                             "separation the scan asks for more than k and may have to come back: use shadow(cuda=True)")
         ksize = self.embedding.kernel.shape[-1]
         if ksize != 0 and ksize != x_context.shape[-1]:
             raise Exception("The embedding kernel should be of the same size as the context.")
